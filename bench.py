@@ -23,9 +23,12 @@ One "step" = one GPU batch = ``--requests-per-gpu`` requests on every rank.
 The closed loop keeps ``(slots + 2) x R`` requests outstanding; the clock runs
 from the completion that ends warmup step W to the one that ends step W + K,
 inside one continuous run (the pipeline stays primed across the boundary).
-N=1 also reports: scores checked against an fp32 CPU forward of the same
-weights, the p50/p99 of an open-loop run at ``--qps`` (fixed offered load), and
-the literal config-2 point (one 512-candidate request per step, concurrency 1).
+A plain run does only that and prints the result line (``--dump-outputs DIR``
+also writes the scores of the last timed step's requests). ``--full`` adds the
+other measurements after the timed steps; N=1 then also reports: scores checked
+against an fp32 CPU forward of the same weights, the p50/p99 of an open-loop
+run at ``--qps`` (fixed offered load), the latency-vs-load sweep, and the
+literal config-2 point (one 512-candidate request per step, concurrency 1).
 
 Launch: ``python bench.py`` (1 GPU) or, for N GPUs,
 ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr
@@ -178,6 +181,17 @@ def parse_args():
                     help="ship raw int64 ids / fp32 weights to the GPU instead of host-narrowed 3-byte / int32 rows "
                          "with fp32 weights")
     ap.add_argument("--json-extra", action="store_true", help="print extra diagnostics to stderr")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else the benchmark measures or checks: the "
+                         "scores of one served request against an fp32 CPU forward, the fixed-QPS latency run "
+                         "(--qps), the latency-vs-load sweep (--qps-sweep), the literal config-2 point, the idle "
+                         "step rate of a cluster, and the replica cache's fresh-stream and oracle hit rates. "
+                         "Without it a run sets up, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed run's last step returned to its clients as DIR/scores.npy "
+                         "(DIR/scores_rank<r>.npy at N > 1): the float32 scores of the last step's worth of "
+                         "timed requests, in request order. Requests and weights are seeded, so two builds run "
+                         "with the same arguments can be compared score for score")
     ap.add_argument("--reference-workload", action="store_true",
                     help="the reference's own run instead (DCNClient.java:25-42, 57-74, 205-241): model DCN, requests "
                          "of 1500 candidates with ids 1..43 and weights 1.0 encoded like the reference client "
@@ -484,6 +498,20 @@ def pct(lat_us, q):
     return round(float(np.percentile(lat_us, q)) * 1e-3, 3) if len(lat_us) else None
 
 
+def dump_outputs(out_dir: str, ctx, responses) -> None:
+    """--dump-outputs: the scores the timed run's last requests returned to
+    their clients (the load generator kept those PredictResponses, by request
+    index), decoded and concatenated in request order, as one float32 array."""
+    from distributed_tf_serving_amd.wire import schema as pb
+    from distributed_tf_serving_amd.wire import tensor as T
+
+    scores = [np.asarray(T.to_ndarray(pb.PredictResponse.FromString(r).outputs["prediction_node"]),
+                         dtype=np.float32).reshape(-1) for r in responses]
+    os.makedirs(out_dir, exist_ok=True)
+    name = "scores.npy" if ctx.world == 1 else f"scores_rank{ctx.rank}.npy"
+    np.save(os.path.join(out_dir, name), np.concatenate(scores))
+
+
 def run_live(a, ctx, cfg, model, eng, B):
     world, rank, dev = ctx.world, ctx.rank, ctx.device
     F = cfg.num_fields
@@ -507,7 +535,7 @@ def run_live(a, ctx, cfg, model, eng, B):
     extra = {}
     if eng.self_checks:  # every bucket's fan-out step vs a local forward of the same rows, at start-up
         extra["self_check"] = {"atol": 1e-5, "buckets": eng.self_checks}
-    if world == 1 and pool:
+    if a.full and world == 1 and pool:
         extra["fp32_check"] = fp32_check(cfg, model, live, pool[0])
     # phase barriers of the main thread: a CPU group of their own (the step's
     # collectives, if any, run on the launcher thread on other communicators)
@@ -557,7 +585,10 @@ def run_live(a, ctx, cfg, model, eng, B):
     steps0 = live.stats()["steps"]
     if pool:
         r = live.run_load(pool, warmup=untimed * n_req, count=a.steps * n_req, concurrency=conc,
-                          threads=a.client_threads, timeout_us=timeout_us)
+                          threads=a.client_threads, timeout_us=timeout_us,
+                          keep_last=n_req if a.dump_outputs else 0)
+        if a.dump_outputs and not r["errors"]:
+            dump_outputs(a.dump_outputs, ctx, r["kept"])
     else:  # a rank without requests (scatter followers): its live server joins rank 0's steps
         r = {"window_us": 0.0, "latency_us": [], "errors": 0, "ok": 0}
     st_load = live.stats()
@@ -571,7 +602,7 @@ def run_live(a, ctx, cfg, model, eng, B):
 
     # fixed offered load (whole node), split over the front-door ranks
     fronts = world if eng.contrib_rows(B) and eng.mode != "scatter" else 1
-    if a.qps > 0:
+    if a.full and a.qps > 0:
         sync()
         q = {"latency_us": [], "errors": 0}
         if pool:
@@ -587,7 +618,7 @@ def run_live(a, ctx, cfg, model, eng, B):
                               "p50_ms": round(float(red[0]), 3), "p99_ms": round(float(red[1]), 3),
                               "errors": int(red[2]), "stages": stage_breakdown(q)}
         extra["p50_at_fixed_qps_ms"] = extra["fixed_qps"]["p50_ms"]
-    fracs = [float(x) for x in a.qps_sweep.split(",") if x.strip()] if a.qps_sweep else []
+    fracs = [float(x) for x in a.qps_sweep.split(",") if x.strip()] if a.full and a.qps_sweep else []
     hs0 = host_sched_counters()
     if fracs:  # every rank takes part (the collectives below); ranks without requests only follow
         # the throughput run's request rate, whole node (slowest rank's window)
@@ -619,7 +650,7 @@ def run_live(a, ctx, cfg, model, eng, B):
     # BASELINE config 2 literally: one 512-candidate request at a time (at N > 1
     # fanned out over every GPU: the reference's topology inside one node)
     sync()
-    if rank == 0 and pool:
+    if a.full and rank == 0 and pool:
         c1 = live.run_load(pool, warmup=20, count=300, concurrency=1, threads=1, timeout_us=timeout_us)
         w = c1["window_us"] * 1e-6
         extra["config2_batch512"] = {"concurrency": 1, "p50_ms": pct(c1["latency_us"], 50),
@@ -631,7 +662,7 @@ def run_live(a, ctx, cfg, model, eng, B):
             "blocked_submits", "narrowed", "narrowed_wts_bf16", "narrowed_wts_implicit")
     extra["server"] = {k: st[k] for k in keys}
     extra["server"]["steps_in_throughput_run"] = st_load["steps"]
-    if control is not None:
+    if a.full and control is not None:
         # an idle cluster launches nothing: no step between the phases' ends
         t0 = st["steps"]
         time.sleep(0.05)
@@ -659,12 +690,15 @@ def run_live(a, ctx, cfg, model, eng, B):
                 "remote_lookups_per_step": round(lookups_per_step, 1),
                 "xgmi_bytes_per_step_per_rank": int(misses * cache.count_scale / steps * cfg.embed_dim * 2),
                 "counted_every": cache.count_scale,
-                # the pool repeats: the same hot set on a fresh draw of the stream
-                "hit_rate_fresh_stream": fresh_hit_rate(cfg, model, ctx),
-                # exact top-k of the served pool's remote-key frequencies: the best
-                # any hot set of k rows can do on this stream
-                "oracle": cache_oracle(a, cfg, model, ctx, len(pool), [cache.cap, int(cache.keys.numel())]),
             }
+            if a.full:
+                extra["embedding_exchange"]["hot_row_cache"].update({
+                    # the pool repeats: the same hot set on a fresh draw of the stream
+                    "hit_rate_fresh_stream": fresh_hit_rate(cfg, model, ctx),
+                    # exact top-k of the served pool's remote-key frequencies: the best
+                    # any hot set of k rows can do on this stream
+                    "oracle": cache_oracle(a, cfg, model, ctx, len(pool), [cache.cap, int(cache.keys.numel())]),
+                })
     if eng.scatter is not None:
         # shared-arena scatter: host->device bytes this rank copied per step (its
         # share of rank 0's batch), gathered from every rank

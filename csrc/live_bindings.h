@@ -336,6 +336,7 @@ void def_live_methods(py::class_<H>& c) {
             if (get("threads")) s.threads = spec["threads"].cast<int>();
             if (get("timeout_us")) s.timeout_us = spec["timeout_us"].cast<int64_t>();
             if (get("seed")) s.seed = spec["seed"].cast<uint64_t>();
+            if (get("keep_last")) s.keep_last = spec["keep_last"].cast<int64_t>();
             if (get("debug_done_delay_us")) s.debug_done_delay_us = spec["debug_done_delay_us"].cast<int64_t>();
             dtfs::runtime::LoadResult r;
             {
@@ -356,6 +357,9 @@ void def_live_methods(py::class_<H>& c) {
             o["wall_us"] = r.wall_us;
             o["first_error"] = r.first_error;
             o["first_error_code"] = r.first_error_code;
+            py::list kept;  // keep_last: the last timed requests' serialized responses, by request index
+            for (const auto& k : r.kept) kept.append(py::bytes(k));
+            o["kept"] = kept;
             return o;
           },
           py::arg("requests"), py::arg("spec"),

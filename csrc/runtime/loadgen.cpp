@@ -72,6 +72,9 @@ LoadResult run_load(LiveServer& srv, const std::vector<std::string>& reqs, const
     stg_sched.assign(size_t(spec.warmup + spec.count), Stages{});
   }
   res.latency_us.reserve(size_t(spec.count));
+  const int64_t keep_end = spec.warmup + spec.count;
+  const int64_t keep_begin = keep_end - std::min(std::max<int64_t>(0, spec.keep_last), spec.count);
+  res.kept.assign(size_t(keep_end - keep_begin), std::string());
   WorkQ work;
   std::atomic<int64_t> next{0};
 
@@ -104,6 +107,7 @@ LoadResult run_load(LiveServer& srv, const std::vector<std::string>& reqs, const
           res.first_error_code = r.code;
         }
       }
+      if (i >= keep_begin && i < keep_end && r.code == kOk) res.kept[size_t(i - keep_begin)] = std::move(r.response);
       if (open_loop) {
         if (i >= spec.warmup && i < spec.warmup + spec.count) {
           lat_sched[size_t(i)] = double(t - t_sched);

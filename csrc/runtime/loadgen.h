@@ -30,6 +30,7 @@ struct LoadSpec {
   int threads = 4;          // submitting threads (each copies its requests into the arena)
   int64_t timeout_us = 0;   // per-request deadline (0 = none)
   uint64_t seed = 1;
+  int64_t keep_last = 0;    // keep the responses of the last keep_last timed requests (LoadResult::kept)
   int64_t debug_done_delay_us = 0;  // test hook: the last request's completion callback sleeps this long
                                     // after its completion is counted (run_load must still wait for it)
 };
@@ -51,6 +52,9 @@ struct LoadResult {
   double wall_us = 0;
   std::string first_error;
   int first_error_code = 0;
+  // LoadSpec::keep_last: serialized responses of requests warmup + count - keep_last .. warmup + count - 1,
+  // by request index (request i is requests[i % size]); a failed request leaves its entry empty
+  std::vector<std::string> kept;
 };
 
 LoadResult run_load(LiveServer& srv, const std::vector<std::string>& requests, const LoadSpec& spec);

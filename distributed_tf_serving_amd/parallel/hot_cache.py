@@ -216,6 +216,9 @@ class HotRowCache:
         self.ring_ctr = torch.zeros(64, **i64)
         self.keys = torch.empty(0, **i64)          # the active hot set, sorted
         self.slots = torch.empty(0, dtype=torch.int32, device=dev)
+        # (keys, slots) published as ONE reference: lookup_cpu runs on the serving
+        # threads while the refresher swaps the set, and must not pair new keys with old slots
+        self._active_set = (self.keys, self.slots)
         self.cand_keys = torch.empty(0, **i64)     # candidates with decayed counts
         self.cand_score = torch.empty(0, dtype=torch.float32, device=dev)
         self.active = -1
@@ -265,12 +268,13 @@ class HotRowCache:
     # -- CPU reference of the kernels' cache side ---------------------------------
     def lookup_cpu(self, keys: torch.Tensor) -> torch.Tensor:
         """Slot of each key in the active set, -1 if absent."""
-        k = self.keys.cpu()
+        k, slots = self._active_set  # one read: a refresh may swap the set meanwhile
+        k = k.cpu()
         if k.numel() == 0:
             return torch.full_like(keys, -1, dtype=torch.int64)
         pos = torch.searchsorted(k, keys).clamp(max=k.numel() - 1)
         found = k[pos] == keys
-        return torch.where(found, self.slots.cpu().long()[pos], torch.full_like(pos, -1))
+        return torch.where(found, slots.cpu().long()[pos], torch.full_like(pos, -1))
 
     def count_cpu(self, hits: int, misses: int) -> None:
         self.stats[0] += hits
@@ -377,6 +381,7 @@ class HotRowCache:
         if cuda:
             self._stream.synchronize()  # the swap's store has landed
         self.keys, self.slots = keys, slots
+        self._active_set = (keys, slots)
         self.active = side
         self.refreshes += 1
         self.last_filled = int(new.numel())

@@ -15,7 +15,7 @@ for rep in $(seq 1 ${REPS:-2}); do
   for arm in "${arms[@]}"; do
     i=$((i + 1))
     log=gpurun_out/ab3/${MODEL:-deepfm}_arm${i}_rep${rep}.log
-    timeout -k 10 240 python -u bench.py --model ${MODEL:-deepfm} --steps ${STEPS:-200} --warmup 20 --qps 0 $arm \
+    timeout -k 10 240 python -u bench.py --full --model ${MODEL:-deepfm} --steps ${STEPS:-200} --warmup 20 --qps 0 $arm \
       > $log 2>&1 || { echo "arm '$arm' failed"; tail -30 $log; exit 1; }
     grep '^{"metric' $log | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print("rep", '$rep', "arm", repr("""'"$arm"'"""), round(d["value"]/1e6,2), "M", d["ms_per_step"], "ms/step", d.get("fp32_check",{}).get("max_abs_diff"))'
   done

@@ -13,7 +13,7 @@ if [ -n "${STUDY:-}" ]; then
   cat gpurun_out/study.log
 fi
 for m in ${MODELS:-}; do
-  timeout -k 10 300 python -u bench.py --model $m --steps ${STEPS:-200} --warmup 20 \
+  timeout -k 10 300 python -u bench.py --full --model $m --steps ${STEPS:-200} --warmup 20 \
     > gpurun_out/bench_$m.log 2>&1 || { echo "bench $m failed"; tail -40 gpurun_out/bench_$m.log; exit 1; }
   grep '^{"metric' gpurun_out/bench_$m.log | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$m', d['value']/1e6, 'M', d['ms_per_step'], 'ms', d.get('fp32_check'), 'fixed_qps p50', d.get('p50_at_fixed_qps_ms'))"
 done

@@ -57,6 +57,36 @@ def test_bench_json_contract(n):
     # value is the whole-job rate: global rows per step / seconds per step
     assert out["value"] == pytest.approx(n * 64 / (out["ms_per_step"] * 1e-3), rel=0.02)
     assert f"candidate-dp{n}" in out["config"]["parallelism"]
+    # a plain run times its steps and nothing else: the other measurements need --full
+    for k in FULL_ONLY:
+        assert k not in out, k
+
+
+FULL_ONLY = ("fp32_check", "fixed_qps", "p50_at_fixed_qps_ms", "latency_vs_load", "config2_batch512")
+
+
+def test_bench_dump_outputs_and_full(tmp_path):
+    """--dump-outputs writes the scores of the last timed step's requests
+    (2 requests x 64 rows here) as float32, identical from run to run and with
+    or without --full; --full adds the other measurements to the same line,
+    among them the served scores checked against the fp32 CPU forward."""
+    import numpy as np
+
+    shape = ("--requests-per-gpu", "2", "--pool", "3")
+    plain = _run_bench(1, (*shape, "--dump-outputs", str(tmp_path / "a")))
+    full = _run_bench(1, (*shape, "--dump-outputs", str(tmp_path / "b"), "--full", "--qps", "200", "--qps-seconds",
+                          "0.2", "--qps-sweep", "0.5"))
+    a, b = np.load(tmp_path / "a" / "scores.npy"), np.load(tmp_path / "b" / "scores.npy")
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == ["scores.npy"]
+    assert a.dtype == np.float32 and a.shape == (128,) and np.all((a > 0) & (a < 1))
+    assert len(np.unique(a[:64])) > 32 and not np.array_equal(a[:64], a[64:])  # two different requests' scores
+    np.testing.assert_array_equal(a, b)
+    assert plain["steps"] == full["steps"] == 2 and not any(k in plain for k in FULL_ONLY)
+    for k in FULL_ONLY:
+        assert k in full, k
+    assert full["fp32_check"]["status"] == "ok" and full["fp32_check"]["rows"] == 64
+    assert full["fixed_qps"]["errors"] == 0 and len(full["latency_vs_load"]["points"]) == 1
+    assert full["config2_batch512"]["p50_ms"] > 0
 
 
 def test_bench_scatter_mode_world2():
@@ -118,7 +148,7 @@ def test_bench_sharded_dlrm_peer_exchange_world2():
     kernels' samples before the clock starts, and the JSON reports its hit
     rate and the bytes that crossed to the peer per step."""
     out = _run_bench(2, ("--model", "dlrm", "--table-rows", "5000", "--exchange", "peer", "--hot-cache-rows", "4096",
-                         "--cache-learn-rounds", "2", "--cache-learn-requests", "16"))
+                         "--cache-learn-rounds", "2", "--cache-learn-requests", "16", "--full"))
     par = out["config"]["parallelism"]
     assert "embedding-mp2" in par and "xGMI" in par and "replica cache" in par, par
     ex = out["embedding_exchange"]

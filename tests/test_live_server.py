@@ -213,6 +213,26 @@ def test_native_load_generator_closed_and_open_loop(server):
     assert all(x > 0 for x in r["latency_us"])
 
 
+@pytest.mark.parametrize("spec", [dict(concurrency=8, threads=3), dict(qps=2000.0, threads=2)])
+def test_native_load_generator_keeps_last_responses(server, spec):
+    """keep_last: the responses of the last timed requests come back by request
+    index (request i is requests[i % len]), whatever order they completed in,
+    and are what a direct call returns for the same request."""
+    live = server.registry.resolve("DCN").scheduler
+    synth = SyntheticRequests(fields=F, seed=6)
+    reqs = [synth.serialized(rows) for rows in (16, 3, 9, 1, 12)]
+    warmup, count, keep = 7, 33, 11
+    r = live.run_load(reqs, warmup=warmup, count=count, keep_last=keep, **spec)
+    assert r["errors"] == 0 and len(r["kept"]) == keep
+    for k, resp in enumerate(r["kept"]):
+        want = _scores(live.predict_bytes(reqs[(warmup + count - keep + k) % len(reqs)], 10.0))
+        got = _scores(resp)
+        assert got.shape == want.shape  # the pool's requests differ in rows: the right request's response
+        np.testing.assert_allclose(got, want, atol=1e-5)  # batched with other rows than the direct call
+    assert live.run_load(reqs, warmup=2, count=8, **spec)["kept"] == []
+    assert len(live.run_load(reqs, warmup=2, count=8, keep_last=100, **spec)["kept"]) == 8  # at most the window
+
+
 def _engine(cfg):
     return build_engine(cfg, device="cpu", slots=2)
 

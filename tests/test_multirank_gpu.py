@@ -49,7 +49,7 @@ def test_bench_ranks_sharing_one_gpu(n, mode, peer, scatter_path):
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus", str(n),
            "--steps", "20", "--warmup", "4", "--prime-steps", "10", "--requests-per-gpu", "4", "--request-rows", "96", "--mode", mode,
            "--pool", "8", "--client-threads", "2", "--qps", "500", "--qps-seconds", "0.4", "--small-buckets", "96",
-           "--step-timeout-s", "20", "--scatter-path", scatter_path]
+           "--step-timeout-s", "20", "--scatter-path", scatter_path, "--full"]
     env = dict(os.environ, DTFS_SHARE_GPU="1", DTFS_HOST_THREADS="2", DTFS_HANG_DUMP_S="100",
                DTFS_PEER_COMM=str(peer))
     p = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=110)
@@ -87,7 +87,7 @@ def test_bench_dcn_v2_alltoall_ranks_sharing_one_gpu(n, peer):
            "--model", "dcn_v2", "--mode", "alltoall", "--steps", "20", "--warmup", "4", "--prime-steps", "10",
            "--requests-per-gpu", "4", "--request-rows", "96", "--pool", "8", "--client-threads", "2",
            "--qps", "200", "--qps-seconds", "0.4", "--qps-sweep", "", "--small-buckets", "96",
-           "--step-timeout-s", "20"]
+           "--step-timeout-s", "20", "--full"]
     env = dict(os.environ, DTFS_SHARE_GPU="1", DTFS_HOST_THREADS="2", DTFS_HANG_DUMP_S="100",
                DTFS_PEER_COMM=str(peer))
     p = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=110)
@@ -115,7 +115,7 @@ def test_bench_eight_ranks_sharing_one_gpu():
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus", "8",
            "--steps", "10", "--warmup", "2", "--prime-steps", "5", "--requests-per-gpu", "4", "--request-rows", "64",
            "--pool", "4", "--client-threads", "1", "--qps", "0", "--qps-sweep", "", "--small-buckets", "64",
-           "--mode", "alltoall", "--step-timeout-s", "60"]
+           "--mode", "alltoall", "--step-timeout-s", "60", "--full"]
     env = dict(os.environ, DTFS_SHARE_GPU="1", DTFS_HOST_THREADS="1", DTFS_HANG_DUMP_S="140")
     p = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=170)
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-4000:])
