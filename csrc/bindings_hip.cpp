@@ -1185,7 +1185,9 @@ torch::Tensor gather_mlp(torch::Tensor table, c10::optional<torch::Tensor> lin, 
               "gather_mlp: table must be contiguous bf16 [V, 64]");
   const int64_t V = table.size(0);
   TORCH_CHECK(F >= 1 && F <= 64, "gather_mlp handles 1..64 fields");
-  TORCH_CHECK(modulo > 0 && modulo <= V, "modulo must be in (0, table rows]");
+  // a modulo past the table is served: the kernel clamps every row into
+  // [0, V) (and hashes with a plain 64-bit modulo from 2^32 up)
+  TORCH_CHECK(modulo > 0, "modulo must be positive");
   for (auto* t : {&W1p, &W2p, &W3p})
     TORCH_CHECK(t->scalar_type() == torch::kBFloat16 && t->is_contiguous(), "W1p / W2p / W3p: contiguous bf16 (pack_frag32)");
   TORCH_CHECK(b1.scalar_type() == torch::kFloat32 && b1.numel() == 1024 && b2.scalar_type() == torch::kFloat32 &&

@@ -11,20 +11,30 @@ namespace kern {
 
 constexpr int kSortMax = 8192;
 
+// Total order on scores as an unsigned key: the IEEE bits made monotonic
+// (-inf lowest, +inf highest, -0.0 == +0.0 so zeros tie like in a comparison
+// sort), inverted for descending; NaN ranks after every number in both modes
+// and padding after NaN.
+constexpr uint32_t kSortKeyNaN = 0xfffffffeu, kSortKeyPad = 0xffffffffu;
+
+__device__ __forceinline__ uint32_t sort_key(float v, bool descending) {
+  if (v != v) return kSortKeyNaN;
+  uint32_t u = v == 0.f ? 0u : __float_as_uint(v);
+  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // [0x007fffff (-inf), 0xff800000 (+inf)]
+  return descending ? ~u : u;
+}
+
 __global__ void __launch_bounds__(1024) bitonic_sort_kernel(const float* __restrict__ in, int n, int descending,
                                                             float* __restrict__ out, int64_t* __restrict__ perm,
                                                             int k_out) {
-  __shared__ float key[kSortMax];
+  __shared__ uint32_t key[kSortMax];
   __shared__ int idx[kSortMax];
   int p2 = 1;
   while (p2 < n) p2 <<= 1;
-  // Always sort ascending on a transformed key (negated for descending), so
-  // ties break by candidate index in both modes; padding and NaN rank last.
+  // Always sort ascending on the transformed key, so ties break by candidate
+  // index in both modes; NaN and padding rank last.
   for (int i = threadIdx.x; i < p2; i += blockDim.x) {
-    float v = i < n ? in[i] : INFINITY;
-    if (v != v) v = INFINITY;
-    else if (descending && i < n) v = -v;
-    key[i] = v;
+    key[i] = i < n ? sort_key(in[i], descending != 0) : kSortKeyPad;
     idx[i] = i < n ? i : 0x7fffffff;
   }
   __syncthreads();
@@ -34,7 +44,7 @@ __global__ void __launch_bounds__(1024) bitonic_sort_kernel(const float* __restr
         const int lo = 2 * i - (i & (stride - 1));
         const int hi = lo + stride;
         const bool up = (lo & size) == 0;
-        const float a = key[lo], b = key[hi];
+        const uint32_t a = key[lo], b = key[hi];
         const int ia = idx[lo], ib = idx[hi];
         // total order: by key, ties by candidate index (stable)
         const bool gt = (a > b) || (a == b && ia > ib);
@@ -48,10 +58,11 @@ __global__ void __launch_bounds__(1024) bitonic_sort_kernel(const float* __restr
       __syncthreads();
     }
   }
+  // the scores themselves, bit for bit (the key folds -0.0 and every NaN)
   for (int i = threadIdx.x; i < k_out; i += blockDim.x) {
-    const float v = key[i];
-    out[i] = (descending && v != INFINITY) ? -v : v;
-    if (perm) perm[i] = idx[i];
+    const int j = idx[i];
+    out[i] = in[j];
+    if (perm) perm[i] = j;
   }
 }
 

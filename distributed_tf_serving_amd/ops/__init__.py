@@ -786,15 +786,19 @@ def unpack_bfrag(Wp: torch.Tensor, N: int, K: int) -> torch.Tensor:
 # ------------------------------------------------------------------ K7
 def sort_scores(scores: torch.Tensor, descending: bool = False, k: int = -1):
     """Sorted scores + the candidate permutation (the reference drops the latter,
-    DCNClient.java:195). GPU: bitonic sort in LDS up to 8192 scores."""
+    DCNClient.java:195). GPU: bitonic sort in LDS up to 8192 scores. Stable
+    (ties, -0.0 == 0.0 included, keep candidate order); NaN scores rank last in
+    both directions; the scores come back bit for bit."""
     n = scores.numel()
     if k < 0 or k > n:
         k = n
     if scores.is_cuda and n <= hip().sort_max_elems():
         s, p = hip().sort_scores(scores.contiguous().float(), descending, int(k))
         return s, p
-    if scores.is_cuda:  # large lists: library sort (plain, not a hot fused op)
-        s, p = torch.sort(scores.float(), descending=descending, stable=True)
-        return s[:k], p[:k]
-    s, p = torch.sort(scores.float(), descending=descending, stable=True)
-    return s[:k], p[:k]
+    # large lists / CPU: library sort (plain, not a hot fused op). torch.sort
+    # ranks NaN first when descending; a second stable pass on the NaN flag
+    # moves them behind every number, like the kernel, in candidate order
+    sf = scores.float()
+    p = torch.sort(sf, descending=descending, stable=True).indices
+    p = p[torch.sort(torch.isnan(sf[p]).to(torch.uint8), stable=True).indices]
+    return sf[p[:k]], p[:k]

@@ -561,7 +561,34 @@ def test_mlp_tail_into_pinned_host_and_model_path(cuda):
     _close(y2, two_kernels(), 2e-3, 2e-3, "mlp_tail after a weight update")
 
 
-@pytest.mark.parametrize("n", [1, 7, 1500, 4096, 8192])
+def _sort_ref_perm(s, desc):
+    """The stable permutation: numbers by value (ties, -0.0 == 0.0 included, in
+    candidate order), then every NaN in candidate order - in both directions."""
+    nan = torch.isnan(s)
+    idx = torch.arange(s.numel())
+    num = idx[~nan]
+    return torch.cat([num[torch.sort(s[num], descending=desc, stable=True).indices], idx[nan]])
+
+
+def _same_bits(a, b):
+    return torch.equal(a.cpu().contiguous().view(torch.int32), b.cpu().contiguous().view(torch.int32))
+
+
+def _check_sort(cuda, s, desc):
+    n = s.numel()
+    v, p = ops.sort_scores(s.to(cuda), descending=desc)
+    pr = _sort_ref_perm(s, desc)
+    assert torch.equal(p.cpu(), pr)  # the stable permutation itself, not only s[perm]
+    assert _same_bits(v, s[p.cpu()])  # out[i] is in[perm[i]] bit for bit (NaN payloads, the sign of zero)
+    nn = int(torch.isnan(s).sum())
+    assert torch.isnan(v.cpu()[n - nn:]).all() and not torch.isnan(v.cpu()[: n - nn]).any()  # NaN ranks last
+    k = min(10, n)
+    v, p = ops.sort_scores(s.to(cuda), descending=True, k=k)
+    pk = _sort_ref_perm(s, True)[:k]
+    assert torch.equal(p.cpu(), pk) and _same_bits(v, s[pk])
+
+
+@pytest.mark.parametrize("n", [1, 7, 1500, 4096, 8192, 8193])  # 8193: past the kernel, the library-sort path
 @pytest.mark.parametrize("desc", [False, True])
 def test_sort(cuda, n, desc):
     s = torch.rand(n)
@@ -572,6 +599,28 @@ def test_sort(cuda, n, desc):
     assert torch.equal(s[p.cpu()], vr)
     v, p = ops.sort_scores(s.to(cuda), descending=True, k=min(10, n))
     assert torch.equal(v.cpu(), torch.sort(s, descending=True).values[: min(10, n)])
+    _check_sort(cuda, s, desc)
+
+
+@pytest.mark.parametrize("n", [7, 1500, 8193])
+@pytest.mark.parametrize("desc", [False, True])
+def test_sort_special_scores(cuda, n, desc):
+    """+-inf, NaN and +-0.0 among the scores, on the kernel and on the
+    library-sort path (n > 8192): infinities keep their sign, NaN ranks last
+    in both directions, zeros of either sign tie in candidate order."""
+    g = torch.Generator().manual_seed(n + desc)
+    s = torch.rand(n, generator=g) - 0.5
+    s[: n // 3] = s[n // 3: 2 * (n // 3)]  # ties
+    special = torch.tensor([float("inf"), float("-inf"), float("nan"), 0.0, -0.0, 0.0, float("nan")])
+    at = torch.randperm(n, generator=g)[:7] if n > 7 else torch.arange(7)
+    s[at] = special
+    if n > 7:  # several of each, scattered
+        more = torch.randperm(n, generator=g)[:70]
+        s[more] = special.repeat(10)
+    _check_sort(cuda, s, desc)
+    # the CPU path of the op ranks the same way
+    v, p = ops.sort_scores(s, descending=desc)
+    assert torch.equal(p, _sort_ref_perm(s, desc)) and _same_bits(v, s[p])
 
 
 @pytest.mark.parametrize("family", ["wdl", "deepfm", "dcn", "dcn_v2", "dlrm"])
