@@ -1412,6 +1412,70 @@ std::vector<torch::Tensor> sort_scores(torch::Tensor s, bool descending, int64_t
   return {out, perm};
 }
 
+// ---------------------------------------------------------------- K7s
+// Device or pinned-host (mapped) buffer of the rank kernels' scores / outputs.
+void check_rank_buf(const torch::Tensor& t, torch::ScalarType dt, const char* name) {
+  TORCH_CHECK(t.is_cuda() || (t.device().is_cpu() && t.is_pinned()), name, " must be on the device or pinned host memory");
+  TORCH_CHECK(t.is_contiguous() && t.dim() == 1 && t.scalar_type() == dt, name, " must be a contiguous 1-D ",
+              c10::toString(dt), " tensor");
+}
+
+std::vector<torch::Tensor> rank_segments(torch::Tensor s, torch::Tensor offsets, bool descending, int64_t k,
+                                         c10::optional<torch::Tensor> out_vals, c10::optional<torch::Tensor> out_idx) {
+  check_dev(s, "scores");
+  TORCH_CHECK(s.scalar_type() == torch::kFloat32 && s.dim() == 1, "scores must be fp32 [N]");
+  TORCH_CHECK(offsets.dim() == 1 && offsets.numel() >= 1 &&
+                  (offsets.scalar_type() == torch::kInt32 || offsets.scalar_type() == torch::kInt64),
+              "offsets must be int32/int64 [S + 1]");
+  const int64_t N = s.numel(), S = offsets.numel() - 1;
+  // the kernel trusts nothing either, but a bad argument is the caller's to hear about
+  const torch::Tensor oh = offsets.to(torch::kCPU, torch::kInt64).contiguous();
+  const int64_t* o = oh.data_ptr<int64_t>();
+  int64_t max_len = 0;
+  if (o[0] < 0) throw py::value_error("rank_segments: offsets must not be negative");
+  for (int64_t i = 0; i < S; ++i) {
+    if (o[i + 1] < o[i]) throw py::value_error("rank_segments: offsets must be ascending");
+    max_len = std::max(max_len, o[i + 1] - o[i]);
+  }
+  if (o[S] > N) throw py::value_error("rank_segments: offsets run past the " + std::to_string(N) + " scores");
+  if (max_len > dtfs::rank_max_elems())
+    throw py::value_error("rank_segments: a segment has " + std::to_string(max_len) + " scores; the kernel ranks at most " +
+                          std::to_string(dtfs::rank_max_elems()));
+  c10::DeviceGuard g(s.device());
+  torch::Tensor vals = out_vals.has_value() ? *out_vals : torch::zeros({N}, s.options());
+  torch::Tensor idx = out_idx.has_value() ? *out_idx : torch::full({N}, -1, s.options().dtype(torch::kInt64));
+  check_dev(vals, "out_vals");
+  check_dev(idx, "out_idx");
+  check_same_dev(s, vals, "out_vals");
+  check_same_dev(s, idx, "out_idx");
+  TORCH_CHECK(vals.scalar_type() == torch::kFloat32 && vals.dim() == 1 && vals.numel() == N, "out_vals must be fp32 [N]");
+  TORCH_CHECK(idx.scalar_type() == torch::kInt64 && idx.dim() == 1 && idx.numel() == N, "out_idx must be int64 [N]");
+  if (S == 0 || max_len == 0) return {vals, idx};
+  const torch::Tensor od = oh.to(torch::kInt32).to(s.device());
+  check_hip(dtfs::launch_rank_segments(s.data_ptr<float>(), N, od.data_ptr<int32_t>(), int(S), int(max_len), descending,
+                                       int(std::max<int64_t>(-1, std::min<int64_t>(k, dtfs::rank_max_elems()))),
+                                       vals.data_ptr<float>(), idx.data_ptr<int64_t>(), cur_stream(s)),
+            "rank_segments");
+  return {vals, idx};
+}
+
+void rank_arena(torch::Tensor arena, torch::Tensor scores, torch::Tensor out_vals, torch::Tensor out_idx) {
+  check_dev(arena, "arena");
+  TORCH_CHECK(arena.scalar_type() == torch::kUInt8 && arena.numel() > dtfs::kArenaPayloadOff, "arena: uint8 [cap]");
+  check_rank_buf(scores, torch::kFloat32, "scores");
+  check_rank_buf(out_vals, torch::kFloat32, "out_vals");
+  check_rank_buf(out_idx, torch::kInt64, "out_idx");
+  const int64_t n = scores.numel();
+  TORCH_CHECK(out_vals.numel() >= n && out_idx.numel() >= n, "out_vals / out_idx must hold the ", n, " scores");
+  for (const auto* t : {&scores, &out_vals, &out_idx})
+    TORCH_CHECK(!t->is_cuda() || t->device() == arena.device(), "rank_arena: buffers must be on ", arena.device());
+  c10::DeviceGuard g(arena.device());
+  // the kernel checks every descriptor against n before it reads or writes
+  check_hip(dtfs::launch_rank_arena(arena.data_ptr(), scores.data_ptr<float>(), n, out_vals.data_ptr<float>(),
+                                    out_idx.data_ptr<int64_t>(), cur_stream(arena)),
+            "rank_arena");
+}
+
 // ---------------------------------------------------------------- fan-out step
 // Validates the device/host buffers of one fan-out step (everything but the
 // per-step H2D source) and computes the per-peer message sizes.
@@ -1568,6 +1632,15 @@ dtfs::runtime::LoopSlot loop_slot_from(const py::dict& d, std::vector<py::object
     if (d.contains("seq") && !d["seq"].is_none()) s.seq = &d["seq"].cast<dtfs::runtime::KernelSequence&>();
     if (d.contains("graph_exec")) s.graph = reinterpret_cast<hipGraphExec_t>(d["graph_exec"].cast<uintptr_t>());
     TORCH_CHECK(s.graph != nullptr || s.seq != nullptr, "slot needs a step graph or kernel sequence");
+    if (d.contains("h_rank_val") && !d["h_rank_val"].is_none()) {
+      torch::Tensor rv = d["h_rank_val"].cast<torch::Tensor>(), ri = d["h_rank_idx"].cast<torch::Tensor>();
+      check_rank_buf(rv, torch::kFloat32, "h_rank_val");
+      check_rank_buf(ri, torch::kInt64, "h_rank_idx");
+      TORCH_CHECK(rv.device().is_cpu() && ri.device().is_cpu() && rv.numel() >= s.h_out_len && ri.numel() >= s.h_out_len,
+                  "h_rank_val / h_rank_idx must be pinned host tensors as long as h_out");
+      s.h_rank_val = rv.data_ptr<float>();
+      s.h_rank_idx = ri.data_ptr<int64_t>();
+    }
   }
   return s;
 }
@@ -1679,6 +1752,13 @@ class GpuBackend : public dtfs::runtime::StepBackend {
   }
   const float* scores(int slot, int b) const override { return slots_[size_t(b)][size_t(slot)].h_out; }
   int64_t scores_len(int slot, int b) const override { return slots_[size_t(b)][size_t(slot)].h_out_len; }
+  // shared-scatter steps run on a share of rank 0's batch: not ranked
+  const float* ranked_scores(int slot, int b) const override {
+    return sc_ ? nullptr : slots_[size_t(b)][size_t(slot)].h_rank_val;
+  }
+  const int64_t* ranked_index(int slot, int b) const override {
+    return sc_ ? nullptr : slots_[size_t(b)][size_t(slot)].h_rank_idx;
+  }
   void abort() override {
     for (auto* c : comms_)
       if (c && !c->aborted()) c->abort();
@@ -1846,6 +1926,10 @@ PYBIND11_MODULE(_hip, m) {
       },
       py::arg("stream"), py::arg("flag"), py::arg("value"));
   m.def("sort_scores", &sort_scores, py::arg("scores"), py::arg("descending") = false, py::arg("k") = -1);
+  m.def("rank_max_elems", &dtfs::rank_max_elems);
+  m.def("rank_segments", &rank_segments, py::arg("scores"), py::arg("offsets"), py::arg("descending") = false,
+        py::arg("k") = -1, py::arg("out_vals") = py::none(), py::arg("out_idx") = py::none());
+  m.def("rank_arena", &rank_arena, py::arg("arena"), py::arg("scores"), py::arg("out_vals"), py::arg("out_idx"));
   m.def("sort_max_elems", &dtfs::sort_max_elems);
 
   py::class_<dtfs::runtime::StepRunner>(m, "StepRunner",

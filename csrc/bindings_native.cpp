@@ -314,12 +314,12 @@ std::vector<std::pair<int64_t, int64_t>> arena_place(torch::Tensor arena, const 
 
 ArenaBatch arena_build(torch::Tensor arena, const std::vector<std::pair<int64_t, int64_t>>& spans,
                        const std::string& ids_key, const std::string& wts_key, int64_t fields, int64_t max_rows,
-                       int64_t varint_chunks) {
+                       int64_t varint_chunks, int64_t n_ranked) {
   check_arena(arena);
   py::gil_scoped_release nogil;
   try {
     return runtime::arena_build(arena.data_ptr<uint8_t>(), arena.numel(), spans, ids_key, wts_key, fields, max_rows,
-                                varint_chunks);
+                                varint_chunks, n_ranked);
   } catch (const std::invalid_argument& e) {
     py::gil_scoped_acquire g;
     throw py::value_error(e.what());
@@ -416,8 +416,11 @@ wire::ModelSpecOut spec_of(const std::string& name, const std::string& sig, py::
 // batching core without a GPU.
 class PyCpuBackend : public runtime::StepBackend {
  public:
+  // ranked: per slot and bucket the (values fp32, indices int64) buffers the
+  // forward fills with the step's ranked scores (ops.rank_arena), or empty
   PyCpuBackend(std::vector<int64_t> buckets, std::vector<std::vector<torch::Tensor>> scores,
-               std::vector<const uint8_t*> arenas, py::function fwd)
+               std::vector<const uint8_t*> arenas, py::function fwd,
+               std::vector<std::vector<std::pair<torch::Tensor, torch::Tensor>>> ranked = {})
       : buckets_(std::move(buckets)), arenas_(std::move(arenas)), fwd_(std::move(fwd)) {
     TORCH_CHECK(!scores.empty(), "need at least one slot");
     for (auto& per_slot : scores) {
@@ -432,6 +435,23 @@ class PyCpuBackend : public runtime::StepBackend {
       scores_.push_back(std::move(v));
     }
     err_.assign(scores_.size(), std::string());
+    TORCH_CHECK(ranked.empty() || ranked.size() == scores_.size(), "ranked: one list per slot");
+    for (size_t s = 0; s < ranked.size(); ++s) {
+      TORCH_CHECK(ranked[s].size() == buckets_.size(), "ranked: one (values, indices) pair per bucket per slot");
+      std::vector<std::pair<const float*, const int64_t*>> v;
+      for (size_t b = 0; b < ranked[s].size(); ++b) {
+        const auto& rv = ranked[s][b].first;
+        const auto& ri = ranked[s][b].second;
+        TORCH_CHECK(rv.device().is_cpu() && rv.is_contiguous() && rv.scalar_type() == torch::kFloat32 &&
+                        rv.numel() >= scores_[s][b].second,
+                    "ranked values must be contiguous CPU fp32 tensors as long as the scores");
+        TORCH_CHECK(ri.device().is_cpu() && ri.is_contiguous() && ri.scalar_type() == torch::kInt64 &&
+                        ri.numel() >= scores_[s][b].second,
+                    "ranked indices must be contiguous CPU int64 tensors as long as the scores");
+        v.emplace_back(rv.data_ptr<float>(), ri.data_ptr<int64_t>());
+      }
+      ranked_.push_back(std::move(v));
+    }
   }
   ~PyCpuBackend() override {
     py::gil_scoped_acquire g;
@@ -457,10 +477,17 @@ class PyCpuBackend : public runtime::StepBackend {
   }
   const float* scores(int slot, int b) const override { return scores_[size_t(slot)][size_t(b)].first; }
   int64_t scores_len(int slot, int b) const override { return scores_[size_t(slot)][size_t(b)].second; }
+  const float* ranked_scores(int slot, int b) const override {
+    return ranked_.empty() ? nullptr : ranked_[size_t(slot)][size_t(b)].first;
+  }
+  const int64_t* ranked_index(int slot, int b) const override {
+    return ranked_.empty() ? nullptr : ranked_[size_t(slot)][size_t(b)].second;
+  }
 
  private:
   std::vector<int64_t> buckets_;
   std::vector<std::vector<std::pair<const float*, int64_t>>> scores_;
+  std::vector<std::vector<std::pair<const float*, const int64_t*>>> ranked_;  // [slot][bucket], or empty
   std::vector<const uint8_t*> arenas_;
   py::function fwd_;
   std::vector<std::string> err_;
@@ -477,7 +504,7 @@ struct PyCpuLive {
 };
 
 PyCpuLive* make_cpu_live(py::dict cfg, std::vector<int64_t> buckets, py::list scores, py::list arenas,
-                         py::function fwd, py::object control) {
+                         py::function fwd, py::object control, py::object ranked) {
   auto* p = new PyCpuLive();
   runtime::StepControl* ctl = dtfs_live::control_from(control, &p->keep);
   auto ar = dtfs_live::arenas_from(arenas, false, &p->keep);
@@ -490,7 +517,20 @@ PyCpuLive* make_cpu_live(py::dict cfg, std::vector<int64_t> buckets, py::list sc
     sc.push_back(std::move(v));
   }
   p->keep.push_back(scores);
-  p->backend = std::make_unique<PyCpuBackend>(std::move(buckets), std::move(sc), std::move(bases), fwd);
+  std::vector<std::vector<std::pair<torch::Tensor, torch::Tensor>>> rk;
+  if (!ranked.is_none()) {
+    for (auto per_slot : ranked.cast<py::list>()) {
+      std::vector<std::pair<torch::Tensor, torch::Tensor>> v;
+      for (auto t : per_slot.cast<py::list>()) {
+        py::tuple pr = t.cast<py::tuple>();
+        TORCH_CHECK(pr.size() == 2, "ranked entries are (values, indices)");
+        v.emplace_back(pr[0].cast<torch::Tensor>(), pr[1].cast<torch::Tensor>());
+      }
+      rk.push_back(std::move(v));
+    }
+    p->keep.push_back(ranked);
+  }
+  p->backend = std::make_unique<PyCpuBackend>(std::move(buckets), std::move(sc), std::move(bases), fwd, std::move(rk));
   p->srv = std::make_unique<runtime::LiveServer>(p->backend.get(), dtfs_live::live_config_from(cfg), std::move(ar),
                                                  ctl);
   return p;
@@ -671,7 +711,7 @@ PYBIND11_MODULE(_native, m) {
   m.def("arena_place", &arena_place, py::arg("arena"), py::arg("requests"), py::arg("start") = 0);
   m.def("arena_build", &arena_build, py::arg("arena"), py::arg("spans"), py::arg("ids_key") = "feat_ids",
         py::arg("wts_key") = "feat_wts", py::arg("fields") = 43, py::arg("max_rows") = int64_t(1) << 40,
-        py::arg("varint_chunks") = 0);
+        py::arg("varint_chunks") = 0, py::arg("n_ranked") = 0);
   m.def("arena_varint_capacity", &runtime::arena_varint_capacity, py::arg("max_rows"), py::arg("fields"),
         py::arg("max_requests") = runtime::kArenaMaxRequests);
   m.def("arena_unpack_cpu", &arena_unpack_cpu, py::arg("arena"), py::arg("packed"), py::arg("fields"));
@@ -760,7 +800,7 @@ PYBIND11_MODULE(_native, m) {
                             "Live serving core (csrc/runtime/live_server.h) with a CPU backend: a Python "
                             "forward(arena_index, slot, bucket_index) scores each batch");
     c.def(py::init(&make_cpu_live), py::arg("config"), py::arg("buckets"), py::arg("scores"), py::arg("arenas"),
-          py::arg("forward"), py::arg("control") = py::none());
+          py::arg("forward"), py::arg("control") = py::none(), py::arg("ranked") = py::none());
     dtfs_live::def_live_methods(c);
   }
   dtfs_live::def_step_control(m);

@@ -316,4 +316,23 @@ int sort_max_elems();
 hipError_t launch_sort_scores(const float* in, int n, bool descending, float* out, int64_t* perm, int k_out,
                               hipStream_t st);
 
+// K7s (rank.hip): S segments of one score buffer ranked in one launch, one
+// workgroup per segment, in launch_sort_scores' order. Segment s is scores
+// [offsets[s], offsets[s + 1]) (device int32, ascending, inside [0, n_scores]);
+// its first k ranks (all when k < 0) go to out_vals / out_idx at the segment's
+// own offsets, the segment-local candidate indices as int64, and ranks past k
+// get 0 / -1. max_len: an upper bound of the segment lengths, which picks the
+// kernel's size class (<= 0: the largest); a segment longer than the class
+// holds, or outside the buffer, is left alone.
+int rank_max_elems();
+hipError_t launch_rank_segments(const float* scores, int64_t n_scores, const int32_t* offsets, int S, int max_len,
+                                bool descending, int k, float* out_vals, int64_t* out_idx, hipStream_t st);
+// The same over the requests of a device request arena (runtime/arena.h):
+// request d's scores are scores[dst_row, dst_row + rows), ranked ascending,
+// every rank kept. The grid returns at once when the header's n_ranked is 0; a
+// descriptor with rows <= 0, rows > rank_max_elems() or rows past scores_len
+// writes nothing. scores / out_vals / out_idx: device or mapped host memory.
+hipError_t launch_rank_arena(const void* arena_dev, const float* scores, int64_t scores_len, float* out_vals,
+                             int64_t* out_idx, hipStream_t st);
+
 }  // namespace dtfs

@@ -254,6 +254,7 @@ inline LiveConfig live_config_from(const py::dict& d) {
   if (get("liveness_only")) c.liveness_only = d["liveness_only"].cast<bool>();
   if (get("narrow_modulo")) c.narrow_modulo = d["narrow_modulo"].cast<int64_t>();
   if (get("narrow_wts_cols")) c.narrow_wts_cols = d["narrow_wts_cols"].cast<int64_t>();
+  if (get("rank_outputs")) c.rank_outputs = d["rank_outputs"].cast<bool>();
   return c;
 }
 
@@ -385,6 +386,7 @@ void def_live_methods(py::class_<H>& c) {
             o["narrowed"] = s.narrowed;
             o["narrowed_wts_bf16"] = s.narrowed_wts_bf16;
             o["narrowed_wts_implicit"] = s.narrowed_wts_implicit;
+            o["ranked"] = s.ranked;
             o["proposed_steps"] = s.proposed_steps;
             o["joined_steps"] = s.joined_steps;
             o["copy_us"] = s.copy_us;

@@ -58,21 +58,23 @@ void arena_varint_cpu(uint8_t* base) {
 }
 
 ArenaBatch arena_build(uint8_t* base, int64_t capacity, const std::vector<Span>& spans, const std::string& ids_key,
-                       const std::string& wts_key, int64_t fields, int64_t max_rows, int64_t varint_chunks) {
+                       const std::string& wts_key, int64_t fields, int64_t max_rows, int64_t varint_chunks,
+                       int64_t n_ranked) {
   std::vector<ArenaItem> items(spans.size());
   for (size_t i = 0; i < spans.size(); ++i) {
     items[i].off = spans[i].first;
     items[i].len = spans[i].second;
   }
-  return arena_build_items(base, capacity, items, ids_key, wts_key, fields, max_rows, varint_chunks);
+  return arena_build_items(base, capacity, items, ids_key, wts_key, fields, max_rows, varint_chunks, 0, 4, n_ranked);
 }
 
 ArenaBatch arena_build_items(uint8_t* base, int64_t capacity, const std::vector<ArenaItem>& items,
                              const std::string& ids_key, const std::string& wts_key, int64_t fields, int64_t max_rows,
-                             int64_t varint_chunks, int64_t narrow_wcols, int64_t narrow_id_bytes) {
+                             int64_t varint_chunks, int64_t narrow_wcols, int64_t narrow_id_bytes, int64_t n_ranked) {
   if (int64_t(items.size()) > kArenaMaxRequests) throw std::invalid_argument("too many requests for one arena");
   if (narrow_wcols < 0 || narrow_wcols > fields) throw std::invalid_argument("narrow_wcols must be in [0, fields]");
   if (narrow_id_bytes != 3 && narrow_id_bytes != 4) throw std::invalid_argument("narrow_id_bytes must be 3 or 4");
+  if (n_ranked < 0 || n_ranked > int64_t(items.size())) throw std::invalid_argument("n_ranked must be in [0, requests]");
   const int64_t idb = narrow_id_bytes;
   const int64_t wcols = narrow_wcols > 0 ? narrow_wcols : fields;  // weights per narrowed row
   uint8_t* payload = base + kArenaPayloadOff;
@@ -334,6 +336,7 @@ ArenaBatch arena_build_items(uint8_t* base, int64_t capacity, const std::vector<
   *reinterpret_cast<int32_t*>(base + 32) = int32_t(n_chunks);
   *reinterpret_cast<int32_t*>(base + 36) = int32_t(narrow_wcols);
   *reinterpret_cast<int32_t*>(base + 40) = int32_t(idb);
+  *reinterpret_cast<int32_t*>(base + 44) = int32_t(n_ranked);
   out.total_rows = row;
   out.n_valid = nd;
   out.n_gpu_varint = int64_t(gjobs.size());

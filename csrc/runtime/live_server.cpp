@@ -60,6 +60,10 @@ LiveServer::LiveServer(StepBackend* backend, LiveConfig cfg, std::vector<std::pa
     throw std::invalid_argument("narrow_modulo must be in [0, 2^31)");
   if (cfg_.narrow_wts_cols < 0 || cfg_.narrow_wts_cols > cfg_.fields)
     throw std::invalid_argument("narrow_wts_cols must be in [0, fields]");
+  ranks_ = cfg_.rank_outputs;
+  for (int b = 0; ranks_ && b < int(bk.size()); ++b)
+    for (int s = 0; ranks_ && s < S; ++s)
+      ranks_ = backend_->ranked_scores(s, b) != nullptr && backend_->ranked_index(s, b) != nullptr;
   paused_ = cfg_.start_paused;
   launcher_ = std::thread([this] { launcher_loop(); });
   completer_ = std::thread([this] { completer_loop(); });
@@ -117,12 +121,22 @@ bool LiveServer::admit(const uint8_t* data, size_t n, int64_t deadline_us, Compl
   if (!v.signature_name.empty() && v.signature_name != cfg_.signature_name)
     return reject(kInvalidArgument, "Serving signature name: \"" + v.signature_name +
                                         "\" not found in signature def of model " + cfg_.model_name);
+  uint8_t want = v.output_filter.empty() ? uint8_t(kWantScores) : uint8_t(0);
   for (const auto& k : v.output_filter) {
-    if (k == cfg_.output_key) continue;
-    if (std::find(cfg_.caller_outputs.begin(), cfg_.caller_outputs.end(), k) != cfg_.caller_outputs.end())
+    if (k == cfg_.output_key) {
+      want |= kWantScores;
+      continue;
+    }
+    if (std::find(cfg_.caller_outputs.begin(), cfg_.caller_outputs.end(), k) != cfg_.caller_outputs.end()) {
+      if (ranks_ && (k == cfg_.sorted_key || k == cfg_.index_key)) {
+        want |= k == cfg_.sorted_key ? kWantSorted : kWantIndex;
+        continue;
+      }
       return reject(kCallerPath, "output " + k + " is produced by the general path");
+    }
     return reject(kInvalidArgument, "output tensor alias not found in signature: " + k);
   }
+  const bool ranked = (want & (kWantSorted | kWantIndex)) != 0;
   const wire::TensorView* ti = v.find(cfg_.ids_key);
   const wire::TensorView* tw = v.find(cfg_.wts_key);
   if (!ti || !tw)
@@ -138,12 +152,22 @@ bool LiveServer::admit(const uint8_t* data, size_t n, int64_t deadline_us, Compl
   wire::ModelSpecOut spec{cfg_.model_name, v.signature_name.empty() ? cfg_.signature_name : v.signature_name,
                           cfg_.version >= 0, cfg_.version};
   if (rows == 0) {
-    wire::TensorOut t;
-    t.key = cfg_.output_key;
-    t.shape = {0};
-    done(Reply{kOk, "", wire::encode_predict_response(spec, {t})});
+    std::vector<wire::TensorOut> outs;
+    for (const uint8_t w : {kWantScores, kWantSorted, kWantIndex}) {
+      if (!(want & w)) continue;
+      wire::TensorOut t;
+      t.key = w == kWantScores ? cfg_.output_key : (w == kWantSorted ? cfg_.sorted_key : cfg_.index_key);
+      t.dtype = w == kWantIndex ? wire::DT_INT64 : wire::DT_FLOAT;
+      t.shape = {0};
+      outs.push_back(std::move(t));
+    }
+    done(Reply{kOk, "", wire::encode_predict_response(spec, outs)});
     return true;
   }
+  // one workgroup ranks one request: longer ones keep the general path
+  if (ranked && rows > kMaxRankedRows)
+    return reject(kCallerPath, "ranked outputs of more than " + std::to_string(kMaxRankedRows) +
+                                   " rows are produced by the general path");
   if (rows > max_rows_)
     return reject(kOversize, "request has " + std::to_string(rows) + " rows; a batch holds at most " +
                                  std::to_string(max_rows_));
@@ -229,6 +253,7 @@ bool LiveServer::admit(const uint8_t* data, size_t n, int64_t deadline_us, Compl
     a = open_;
     Arena& o = arenas_[size_t(a)];
     Pending p{0, int64_t(n), rows, deadline_us, t0, std::move(done)};
+    p.want = want;
     if (narrow) {
       p.narrow = true;
       p.ids_off = align64(o.used);
@@ -515,8 +540,10 @@ void LiveServer::launcher_loop() {
     for (auto& p : pend) (p.deadline_us > 0 && t0 > p.deadline_us ? expired : live).push_back(std::move(p));
     if (!expired.empty()) fail_all(expired, kDeadlineExceeded, "request deadline exceeded while queued");
     std::vector<ArenaItem> items(live.size());
+    int64_t n_ranked = 0;  // arena header: 0 lets the step's rank kernel return at once
     for (size_t i = 0; i < live.size(); ++i) {
       const Pending& p = live[i];
+      if (p.want & (kWantSorted | kWantIndex)) ++n_ranked;
       ArenaItem& it = items[i];
       it.off = p.off;
       it.len = p.len;
@@ -531,7 +558,7 @@ void LiveServer::launcher_loop() {
     try {
       trace::Range tr("live_build");
       batch = arena_build_items(ar.base, ar.capacity, items, cfg_.ids_key, cfg_.wts_key, cfg_.fields, max_rows_,
-                                cfg_.varint_chunks, cfg_.narrow_wts_cols, narrow_id_bytes());
+                                cfg_.varint_chunks, cfg_.narrow_wts_cols, narrow_id_bytes(), n_ranked);
     } catch (const std::exception& e) {
       fail_all(live, kInternal, std::string("batch build failed: ") + e.what());
       if (agree_) {  // the other ranks launch step k: this rank cannot skip it
@@ -674,7 +701,10 @@ void LiveServer::completer_loop() {
     }
     const float* sc = backend_->scores(f.slot, f.bucket);
     const int64_t sc_len = backend_->scores_len(f.slot, f.bucket);
-    int64_t n_ok = 0, n_bad = 0;
+    const float* rk_val = backend_->ranked_scores(f.slot, f.bucket);
+    const int64_t* rk_idx = backend_->ranked_index(f.slot, f.bucket);
+    int64_t n_ok = 0, n_bad = 0, n_ranked = 0;
+    std::vector<wire::TensorOut> outs;
     {
       trace::Range tr("live_encode");
       for (size_t i = 0; i < f.pend.size(); ++i) {
@@ -689,14 +719,32 @@ void LiveServer::completer_loop() {
           r.code = kInternal;
           r.message = "scores buffer smaller than the batch";
           ++n_bad;
+        } else if ((p.want & (kWantSorted | kWantIndex)) && (!rk_val || !rk_idx)) {
+          r.code = kInternal;
+          r.message = "the step produced no ranked outputs";
+          ++n_bad;
         } else {
-          wire::TensorOut t;
-          t.key = cfg_.output_key;
-          t.dtype = wire::DT_FLOAT;
-          t.shape = {f.batch.rows[i]};
-          t.data = sc + f.batch.offsets[i];
-          t.n = f.batch.rows[i];
-          r.response = wire::encode_predict_response(spec, {t});
+          // prediction_node, sorted_prediction, sorted_index: the order of the
+          // general path (serving/service.py _outputs)
+          outs.clear();
+          for (const uint8_t w : {kWantScores, kWantSorted, kWantIndex}) {
+            if (!(p.want & w)) continue;
+            wire::TensorOut t;
+            t.shape = {f.batch.rows[i]};
+            t.n = f.batch.rows[i];
+            if (w == kWantIndex) {
+              t.key = cfg_.index_key;
+              t.dtype = wire::DT_INT64;
+              t.data = rk_idx + f.batch.offsets[i];
+            } else {
+              t.key = w == kWantScores ? cfg_.output_key : cfg_.sorted_key;
+              t.dtype = wire::DT_FLOAT;
+              t.data = (w == kWantScores ? sc : rk_val) + f.batch.offsets[i];
+            }
+            outs.push_back(std::move(t));
+          }
+          r.response = wire::encode_predict_response(spec, outs);
+          if (p.want & (kWantSorted | kWantIndex)) ++n_ranked;
           ++n_ok;
         }
         r.t_arrive = p.t_arrive;
@@ -712,6 +760,7 @@ void LiveServer::completer_loop() {
       std::lock_guard<std::mutex> lk(mu_);
       pending_ -= int64_t(f.pend.size());
       st_.completed += n_ok;
+      st_.ranked += n_ranked;
       st_.failed += n_bad;
       st_.wait_us += double(t1 - t0);
       st_.encode_us += double(t2 - t1);

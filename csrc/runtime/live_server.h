@@ -85,6 +85,12 @@ class StepBackend {
   virtual bool wait(int slot, int64_t timeout_us, std::string* err) = 0;
   virtual const float* scores(int slot, int b) const = 0;
   virtual int64_t scores_len(int slot, int b) const = 0;
+  // The slot's ranked scores, when its step ranks every request of the batch
+  // (csrc/kernels/rank.hip; a CPU backend's forward does the same): request
+  // i's scores in ascending order at [offsets[i], offsets[i] + rows[i]) and the
+  // request-local candidate index of each. nullptr: this slot does not rank.
+  virtual const float* ranked_scores(int /*slot*/, int /*b*/) const { return nullptr; }
+  virtual const int64_t* ranked_index(int /*slot*/, int /*b*/) const { return nullptr; }
   // Called once when the server gives up on the device (stuck step / error):
   // abort communicators so peers stop waiting on this rank.
   virtual void abort() {}
@@ -132,7 +138,13 @@ struct LiveConfig {
   // general path produces: a request naming one in output_filter gets
   // kCallerPath instead of INVALID_ARGUMENT
   std::vector<std::string> caller_outputs;
+  // The step ranks (ServingConfig.rank_on_gpu): when every slot of the backend
+  // has ranked buffers, requests naming sorted_key / index_key are served here
+  // instead of getting kCallerPath, up to kMaxRankedRows rows each.
+  bool rank_outputs = false;
+  std::string sorted_key = "sorted_prediction", index_key = "sorted_index";
 };
+constexpr int64_t kMaxRankedRows = 16384;  // csrc/kernels/rank.hip: one workgroup's segment
 
 struct LiveStats {
   int64_t submitted = 0, rejected = 0, completed = 0, failed = 0, expired = 0;
@@ -140,6 +152,7 @@ struct LiveStats {
   int64_t full_steps = 0, timeout_steps = 0, eager_steps = 0, blocked_submits = 0, narrowed = 0;
   // narrowed requests whose weights travelled as bf16 (all exact) / not at all (all 1.0)
   int64_t narrowed_wts_bf16 = 0, narrowed_wts_implicit = 0;
+  int64_t ranked = 0;  // completed requests that got a ranked output from the step
   // cluster mode: steps this rank proposed / joined with a batch of its own /
   // joined with nothing queued (empty_steps counts those too)
   int64_t proposed_steps = 0, joined_steps = 0;
@@ -192,7 +205,10 @@ class LiveServer {
     bool narrow = false;
     int64_t ids_off = 0, wts_off = 0;  // narrow: payload offsets of the 3-byte / int32 rows and the weights
     int wkind = 0;                     // narrow: WtsKind of the weights (runtime/narrow.h)
+    // outputs the request's filter names (kWant*); an empty filter: kWantScores
+    uint8_t want = 1;
   };
+  enum : uint8_t { kWantScores = 1, kWantSorted = 2, kWantIndex = 4 };
   struct Arena {
     uint8_t* base = nullptr;
     int64_t capacity = 0;
@@ -222,6 +238,7 @@ class LiveServer {
   StepControl* agree_ = nullptr;  // ctl_ unless liveness_only: every step agreed with the other ranks
   int64_t max_rows_ = 0;
   int64_t arena_budget_ = 0;  // payload bytes a batch may plan for (see need_of)
+  bool ranks_ = false;        // cfg_.rank_outputs and every slot of the backend has ranked buffers
 
   mutable std::mutex mu_;
   std::condition_variable cv_launch_;  // launcher: new work / slot freed / writers done

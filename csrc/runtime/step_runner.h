@@ -126,6 +126,10 @@ struct LoopSlot {
   StepProgram prog;                  // programmed step (embedding-parallel models)
   const float* h_out = nullptr;      // pinned scores of the slot
   int64_t h_out_len = 0;
+  // local step that ends with the rank kernel (csrc/kernels/rank.hip): pinned
+  // ranked scores / request-local candidate indices, h_out_len each; else null
+  const float* h_rank_val = nullptr;
+  const int64_t* h_rank_idx = nullptr;
 };
 
 class StepRunner {

@@ -95,6 +95,9 @@ class ServingConfig:
     # shared request arenas (csrc/runtime/shared_scatter.h); "rccl" = RCCL scatter
     scatter_path: str = "shared"
     narrow_ingest: bool = True        # GPU live server: int64 ids -> 3-byte / int32 table rows on the host (fp32 weights)
+    # the served step ends with the segmented rank kernel (csrc/kernels/rank.hip) and the live server answers
+    # requests naming sorted_prediction / sorted_index itself instead of handing them to the general path
+    rank_on_gpu: bool = False
 
 
 @dataclass

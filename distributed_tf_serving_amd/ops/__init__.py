@@ -12,7 +12,8 @@ Every op dispatches on the device of its inputs:
 Op inventory: K0 ``pack_ids``, K1 ``embed``, K1b
 ``embedding_bag``, K2 FM (fused in ``embed``), K3 ``cross_v1``, K3b
 ``cross_v2`` / ``linear_fp8``, K4 ``linear``, K5 ``dot_interaction``, K6
-``head``, K4+K6 ``linear_head``, K7 ``sort_scores``.
+``head``, K4+K6 ``linear_head``, K7 ``sort_scores``, K7s ``rank_segments`` /
+``rank_arena``.
 """
 from __future__ import annotations
 
@@ -802,3 +803,78 @@ def sort_scores(scores: torch.Tensor, descending: bool = False, k: int = -1):
     p = torch.sort(sf, descending=descending, stable=True).indices
     p = p[torch.sort(torch.isnan(sf[p]).to(torch.uint8), stable=True).indices]
     return sf[p[:k]], p[:k]
+
+
+# ------------------------------------------------------------------ K7s
+RANK_MAX = 16384  # scores one workgroup ranks (csrc/kernels/rank.hip): the largest served bucket
+
+
+def rank_segments(scores: torch.Tensor, offsets, descending: bool = False, k: int = -1, out=None):
+    """:func:`sort_scores` over S independent segments of one fp32 score
+    buffer in one launch: segment s is ``scores[offsets[s]:offsets[s + 1]]``
+    (``offsets``: S + 1 ascending ints). Returns (values [N] fp32, index [N]
+    int64) in the buffer's own layout: a segment's ranked scores and their
+    segment-local candidate indices at the segment's offsets; inside a segment
+    positions past ``k`` hold 0 and -1. ``out=(values, index)`` is written in
+    place, and scores outside every segment stay as they are there (0 / -1 in
+    fresh outputs). GPU: one workgroup per segment of at most RANK_MAX scores."""
+    if scores.dim() != 1:
+        raise ValueError("scores must be a 1-D tensor")
+    N = scores.numel()
+    off = torch.as_tensor(offsets).detach().to("cpu", torch.int64).reshape(-1)
+    if off.numel() < 1:
+        raise ValueError("offsets must hold at least one entry")
+    lens = off[1:] - off[:-1]
+    if int(off[0]) < 0 or bool((lens < 0).any()):
+        raise ValueError("offsets must be ascending and not negative")
+    if int(off[-1]) > N:
+        raise ValueError(f"offsets run past the {N} scores")
+    if scores.is_cuda:
+        if lens.numel() and int(lens.max()) > RANK_MAX:
+            raise ValueError(f"a segment has {int(lens.max())} scores; the kernel ranks at most {RANK_MAX}")
+        ov, oi = (None, None) if out is None else out
+        v, i = hip().rank_segments(scores.contiguous().float(), off, bool(descending), int(k), ov, oi)
+        return v, i
+    sf = scores.float()
+    if out is None:
+        vals, idx = torch.zeros(N), torch.full((N,), -1, dtype=torch.int64)
+    else:
+        vals, idx = out
+    for a, b in zip(off[:-1].tolist(), off[1:].tolist()):
+        if b > a:
+            _rank_into(sf, a, b, descending, k, vals, idx)
+    return vals, idx
+
+
+def _rank_into(sf, a, b, descending, k, vals, idx) -> None:
+    s, p = sort_scores(sf[a:b], descending, k)
+    kk = s.numel()
+    vals[a:a + kk] = s
+    idx[a:a + kk] = p
+    vals[a + kk:b] = 0
+    idx[a + kk:b] = -1
+
+
+def rank_arena(arena: torch.Tensor, scores: torch.Tensor, out_vals: torch.Tensor, out_idx: torch.Tensor) -> None:
+    """Rank every request of a built request arena (serving/arena.py) in one
+    launch: request d's scores ``scores[dst_row:dst_row + rows]`` ascending into
+    ``out_vals`` and their request-local candidate indices into ``out_idx``
+    (int64), at the same offsets. Nothing is written when the header's
+    ``n_ranked`` is 0, nor for a request that does not fit ``scores`` or has
+    more than RANK_MAX rows. GPU: ``arena`` on the device, the other three on
+    the device or in pinned host memory (capturable: no allocation, no sync).
+    CPU: the same header and descriptors read from the host arena."""
+    if arena.is_cuda:
+        hip().rank_arena(arena, scores, out_vals, out_idx)
+        return
+    hdr = arena[:64].contiguous().view(torch.int32)
+    n_req, n_ranked = int(hdr[0]), int(hdr[11])
+    if n_ranked <= 0:
+        return
+    n_req = min(n_req, native().ARENA_MAX_REQUESTS)
+    desc = arena[64:64 + 32 * n_req].contiguous().view(torch.int64).reshape(n_req, 4)
+    n = scores.numel()
+    for rows, r0 in desc[:, 2:].tolist():
+        if rows <= 0 or rows > RANK_MAX or r0 < 0 or r0 + rows > n:
+            continue
+        _rank_into(scores, r0, r0 + rows, False, -1, out_vals, out_idx)

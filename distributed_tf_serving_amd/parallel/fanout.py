@@ -126,7 +126,8 @@ class StepHandle:
 class FanoutEngine:
     def __init__(self, executor: ShardExecutor, ctx: DistContext, mode: str = "alltoall", group=None,
                  step_graphs: bool = True, native_launch: bool = True, ingest: str = "packed", arena=None,
-                 native_fanout: bool = True, force_fanout: bool = False, shared_scatter=None):
+                 native_fanout: bool = True, force_fanout: bool = False, shared_scatter=None,
+                 rank_on_gpu: bool = False):
         """``ingest="packed"``: the host decodes into packed rows (host_in) and
         the H2D moves rows. ``ingest="arena"``: the host only parses request
         framing into a request arena (serving/arena.py); the H2D moves the raw
@@ -136,7 +137,11 @@ class FanoutEngine:
         from C++ (StepRunner.launch_fanout) with native RCCL communicators
         (csrc/comm) - ingress and egress exchanges on their own streams and
         communicators, overlapping the forward graph. ``force_fanout`` keeps
-        the fan-out mode on a 1-rank job (exercises that path on one GPU)."""
+        the fan-out mode on a 1-rank job (exercises that path on one GPU).
+
+        ``rank_on_gpu`` (arena ingest): a local step also ranks every
+        request's scores (``ops.rank_arena`` after the forward, in the step's
+        graph) into :meth:`host_rank`, for the live server's ranked outputs."""
         if mode not in MODES:
             raise ValueError(f"mode must be one of {MODES}")
         if ingest not in ("packed", "arena"):
@@ -145,6 +150,8 @@ class FanoutEngine:
             raise ValueError("arena ingest needs an ArenaLayout")
         self.ingest = ingest
         self.arena = arena
+        self.rank_on_gpu = bool(rank_on_gpu) and ingest == "arena"
+        self._host_rank: Dict[Tuple[int, int], Tuple[torch.Tensor, torch.Tensor]] = {}
         self._host_arena: Dict[int, torch.Tensor] = {}
         self._dev_arena: Dict[int, torch.Tensor] = {}
         self.ex = executor
@@ -218,6 +225,26 @@ class FanoutEngine:
         if t is None:
             t = torch.zeros(max(1, self.contrib_rows(B)), dtype=torch.float32, pin_memory=self.cuda)
             self._host_out[key] = t
+        return t
+
+    @property
+    def ranks_steps(self) -> bool:
+        """This engine's steps rank their requests: ``rank_on_gpu`` on a local
+        step (a GPU's captured step graph, or the CPU forward); fan-out,
+        shared-scatter and programmed steps do not."""
+        if not self.rank_on_gpu or self.mode != "local" or self.scatter is not None:
+            return False
+        return not self.cuda or (self._step_graphs_enabled() and not self._program_buckets)
+
+    def host_rank(self, B: int, slot: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(ranked scores fp32 [B], candidate indices int64 [B]) of a (bucket,
+        slot), beside host_out (pinned on a GPU engine)."""
+        key = (B, slot)
+        t = self._host_rank.get(key)
+        if t is None:
+            n = max(1, self.contrib_rows(B))
+            t = self._host_rank[key] = (torch.zeros(n, dtype=torch.float32, pin_memory=self.cuda),
+                                        torch.zeros(n, dtype=torch.int64, pin_memory=self.cuda))
         return t
 
     def step_out(self, B: int, slot: int = 0) -> torch.Tensor:
@@ -580,8 +607,10 @@ class FanoutEngine:
             elif self._step_graphs_enabled():
                 self._capture_step(B, s)
                 g = self._step_graph[(B, s)]
-                out.append(dict(h2d_dst=self.dev_arena(s), graph_exec=g.raw_cuda_graph_exec(), seq=seq(g),
-                                h_out=h_out))
+                slot = dict(h2d_dst=self.dev_arena(s), graph_exec=g.raw_cuda_graph_exec(), seq=seq(g), h_out=h_out)
+                if self.ranks_steps:
+                    slot["h_rank_val"], slot["h_rank_idx"] = self.host_rank(B, s)
+                out.append(slot)
             elif self.native_fanout_active:
                 key = (B, s)
                 g_res, fwd, scores = self._forward_parts(B, s)
@@ -634,8 +663,9 @@ class FanoutEngine:
         arena_dev = self.dev_arena(slot) if self.ingest == "arena" else None
 
         fused_ingest = arena_dev is not None and getattr(self.ex.model, "supports_arena", False)
+        rank = self.host_rank(B, slot) if self.ranks_steps else None
 
-        def body():
+        def forward():
             # the head kernel writes the scores straight into pinned host memory
             # (no D2H copy node, which a graph would run as a blit kernel)
             if fused_ingest:  # K0 fused into K1: the gather reads the request bytes
@@ -645,6 +675,16 @@ class FanoutEngine:
             if arena_dev is not None:  # K0 on the GPU: request bytes -> packed rows
                 self._unpack(arena_dev, buf)
             self.ex._forward(buf, out=out)
+
+        def body():
+            forward()
+            if rank is not None:
+                # every request's scores ranked in one launch (it returns at
+                # once when no request of the batch asked): scores read from,
+                # and ranks written to, pinned host memory like the head's
+                from .. import ops
+
+                ops.rank_arena(arena_dev, out, rank[0], rank[1])
 
         side = torch.cuda.Stream(self.dev)
         side.wait_stream(cur)

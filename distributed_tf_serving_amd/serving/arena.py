@@ -10,7 +10,9 @@ decoded on the host into arena scratch space in raw form, so the GPU side is
 uniform.
 
 Layout (shared with csrc): header (n_req int32 @0, total_rows int64 @8,
-row_table_off int64 @16), descriptors {ids_off, wts_off, rows, dst_row} int64
+row_table_off int64 @16, n_ranked int32 @44: how many requests of the batch
+asked for a ranked output - 0 lets the step's rank kernel return at once),
+descriptors {ids_off, wts_off, rows, dst_row} int64
 @64, payload @ARENA_PAYLOAD_OFF; after the last request (and any scratch) a row
 table {ids_off, wts_off} int32 per candidate row, so a GPU thread finds its
 row's features with one load instead of a search over the descriptors.
@@ -73,10 +75,12 @@ class ArenaLayout:
         """Copy serialized requests into the payload region; returns their spans."""
         return native().arena_place(arena, list(requests), start)
 
-    def build(self, arena: torch.Tensor, spans: Sequence[Tuple[int, int]], ids_key="feat_ids", wts_key="feat_wts"):
-        """Parse in place + write descriptors; returns ArenaBatch (rows/offsets/errors/used_bytes)."""
+    def build(self, arena: torch.Tensor, spans: Sequence[Tuple[int, int]], ids_key="feat_ids", wts_key="feat_wts",
+              n_ranked: int = 0):
+        """Parse in place + write descriptors; returns ArenaBatch (rows/offsets/errors/used_bytes).
+        ``n_ranked``: the header's count of requests that asked for a ranked output."""
         return native().arena_build(arena, list(spans), ids_key, wts_key, self.fields, self.max_rows,
-                                    self.varint_chunks)
+                                    self.varint_chunks, int(n_ranked))
 
     def unpack_cpu(self, arena: torch.Tensor, packed: torch.Tensor) -> torch.Tensor:
         native().arena_unpack_cpu(arena, packed, self.fields)

@@ -113,6 +113,10 @@ class LiveScheduler:
             start_paused=start_paused, narrow_modulo=self.narrow_modulo, narrow_wts_cols=self.narrow_wts_cols,
             liveness_only=bool(liveness_only and control is not None),
             caller_outputs=["sorted_prediction", "sorted_index"])  # service.RANKED_OUTPUTS
+        # ranked outputs from the step itself (ServingConfig.rank_on_gpu, local
+        # steps only): the native server answers them; otherwise CALLER_PATH
+        self.ranks = bool(getattr(sc, "rank_on_gpu", False)) and bool(getattr(engine, "ranks_steps", False))
+        self.config["rank_outputs"] = self.ranks
         if engine.cuda:
             from ..ops import hip
 
@@ -129,10 +133,16 @@ class LiveScheduler:
             scores = [[engine.host_out(B, s) for B in self.buckets] for s in range(slots)]
             buckets = self.buckets
 
+            ranked = [[engine.host_rank(B, s) for B in self.buckets] for s in range(slots)] if self.ranks else None
+
             def forward(ai: int, slot: int, b: int) -> None:
                 engine.launch(buckets[b], slot, src=self.arenas[ai], nbytes=self.layout.capacity).wait()
+                if ranked is not None:  # the host form of the GPU step's rank kernel
+                    from .. import ops
 
-            self.srv = native().LiveServer(self.config, self.step_rows, scores, self.arenas, forward, control)
+                    ops.rank_arena(self.arenas[ai], scores[slot][b], *ranked[slot][b])
+
+            self.srv = native().LiveServer(self.config, self.step_rows, scores, self.arenas, forward, control, ranked)
         self.control = control
         self.max_rows = int(self.srv.max_rows)
         self.OVERSIZE = int(native().STATUS_OVERSIZE)

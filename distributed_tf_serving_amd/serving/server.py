@@ -96,7 +96,8 @@ def build_engine(cfg: Config, device=None, slots: int = 3, ctx: Optional[DistCon
             nm, nw = live_narrowing(model, dev.type == "cuda", bool(getattr(sc, "narrow_ingest", True)))
             seg = scatter_for_engine(ctx, cfg.model.num_fields, arena.capacity, slots, max(buckets),
                                      tag=scatter_tag, store=store, narrow_modulo=nm, narrow_wts_cols=nw)
-        eng = FanoutEngine(ex, ctx, mode=mode, ingest="arena", group=group, arena=arena, shared_scatter=seg)
+        eng = FanoutEngine(ex, ctx, mode=mode, ingest="arena", group=group, arena=arena, shared_scatter=seg,
+                           rank_on_gpu=bool(getattr(sc, "rank_on_gpu", False)))
     else:
         eng = FanoutEngine(ex, ctx, mode=mode, group=group)
     for B in buckets:
