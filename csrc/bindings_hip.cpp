@@ -1165,6 +1165,52 @@ torch::Tensor mlp_tail(torch::Tensor X, torch::Tensor W2p, torch::Tensor b2, int
   return y;
 }
 
+// The same tail on the block-scaled fp8 matrix cores (mlp_tail_fp8.hip): the
+// kernel MX-quantises X and h2 itself. W2p / W3p: e4m3 weights in the 16x16x128
+// fragment order (ops.pack_bfrag_fp8); sw2 / sw3: per-output-channel scales.
+torch::Tensor mlp_tail_fp8(torch::Tensor X, torch::Tensor W2p, torch::Tensor sw2, torch::Tensor b2, int64_t act2,
+                           torch::Tensor W3p, torch::Tensor sw3, torch::Tensor b3, int64_t act3, torch::Tensor hw,
+                           double hbias, c10::optional<torch::Tensor> extra, bool sigmoid,
+                           c10::optional<torch::Tensor> out) {
+  constexpr int64_t K1 = 1024, N2 = 512, N3 = 256;
+  check_gpu(X, "X");
+  for (auto* t : {&W2p, &sw2, &b2, &W3p, &sw3, &b3, &hw}) {
+    check_dev(*t, "mlp_tail_fp8 operand");
+    check_same_dev(X, *t, "mlp_tail_fp8 operand");
+  }
+  TORCH_CHECK(X.scalar_type() == torch::kBFloat16 && X.dim() == 2 && X.size(1) == K1, "X must be bf16 [M, 1024]");
+  const int64_t M = X.size(0);
+  TORCH_CHECK(M < (int64_t(1) << 31), "mlp_tail_fp8: row count");
+  TORCH_CHECK(X.stride(1) == 1 && (M <= 1 || (X.stride(0) >= K1 && X.stride(0) % 8 == 0)) &&
+                  reinterpret_cast<uintptr_t>(X.data_ptr()) % 16 == 0,
+              "X needs unit column stride and 16-byte aligned rows");
+  TORCH_CHECK(W2p.scalar_type() == torch::kFloat8_e4m3fn && W3p.scalar_type() == torch::kFloat8_e4m3fn,
+              "W2p, W3p must be e4m3 (pack_bfrag_fp8)");
+  TORCH_CHECK(W2p.numel() == N2 * K1 && W3p.numel() == N3 * N2, "packed weight sizes: 512 x 1024 and 256 x 512");
+  for (auto* t : {&sw2, &b2, &sw3, &b3, &hw})
+    TORCH_CHECK(t->scalar_type() == torch::kFloat32, "sw2, b2, sw3, b3, hw must be fp32");
+  TORCH_CHECK(sw2.numel() == N2 && b2.numel() == N2, "sw2, b2 must have 512 elements");
+  TORCH_CHECK(sw3.numel() == N3 && b3.numel() == N3 && hw.numel() == N3, "sw3, b3, hw must have 256 elements");
+  TORCH_CHECK((act2 == 0 || act2 == 1) && (act3 == 0 || act3 == 1), "act must be 0 (none) or 1 (relu)");
+  if (extra) {
+    check_gpu(*extra, "extra");
+    check_same_dev(X, *extra, "extra");
+    check_extra(*extra, M);
+  }
+  if (out && out->is_cuda()) check_same_dev(X, *out, "out");
+  c10::DeviceGuard g(X.device());
+  torch::Tensor y;
+  float* yp = score_out(X, M, out, y);
+  check_hip(dtfs::launch_mlp_tail_fp8(X.data_ptr(), M <= 1 ? K1 : X.stride(0), int(M), int(K1), W2p.data_ptr(),
+                                      sw2.data_ptr<float>(), b2.data_ptr<float>(), int(act2), int(N2), W3p.data_ptr(),
+                                      sw3.data_ptr<float>(), b3.data_ptr<float>(), int(act3), int(N3),
+                                      hw.data_ptr<float>(), float(hbias),
+                                      extra ? extra->data_ptr<float>() : nullptr, extra ? extra_rows(*extra) : 0,
+                                      extra ? extra_stride(*extra) : 0, sigmoid ? 2 : 0, yp, cur_stream(X)),
+            "mlp_tail_fp8");
+  return y;
+}
+
 // K1 + K2 + K4 x 3 + K6: the whole DeepFM / Wide&Deep tower in one launch,
 // the resolve pass included (gather_mlp.hip): 64 rows x all 1024 h1 columns per
 // workgroup, h1 / h2 kept in LDS. W1p / W2p / W3p: ops.pack_frag32 of the three
@@ -1880,6 +1926,10 @@ PYBIND11_MODULE(_hip, m) {
   m.def("mlp_tail", &mlp_tail, py::arg("X"), py::arg("W2p"), py::arg("b2"), py::arg("act2"), py::arg("W3p"),
         py::arg("b3"), py::arg("act3"), py::arg("hw"), py::arg("hbias") = 0.0, py::arg("extra") = py::none(),
         py::arg("sigmoid") = true, py::arg("out") = py::none());
+  m.def("mlp_tail_fp8", &mlp_tail_fp8, py::arg("X"), py::arg("W2p"), py::arg("sw2"), py::arg("b2"), py::arg("act2"),
+        py::arg("W3p"), py::arg("sw3"), py::arg("b3"), py::arg("act3"), py::arg("hw"), py::arg("hbias") = 0.0,
+        py::arg("extra") = py::none(), py::arg("sigmoid") = true, py::arg("out") = py::none(),
+        "MX-fp8 two-layer MLP tail + head in one launch, operands quantised in-kernel (mlp_tail_fp8.hip)");
   m.def("gather_mlp", &gather_mlp, py::arg("table"), py::arg("lin"), py::arg("arena"), py::arg("ids"),
         py::arg("wts"), py::arg("B"), py::arg("F"), py::arg("modulo"), py::arg("bias"), py::arg("W1p"), py::arg("b1"),
         py::arg("W2p"), py::arg("b2"), py::arg("act2"), py::arg("W3p"), py::arg("b3"), py::arg("act3"), py::arg("hw"),

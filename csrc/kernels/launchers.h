@@ -171,6 +171,17 @@ hipError_t launch_mlp_tail(const void* X, int64_t ldx, int M, int K1, const void
                            int N2, const void* W3p, const float* b3, int act3, int N3, const float* hw, float hbias,
                            const float* extra, int extra_n, int64_t extra_ld, int out_act, float* y, hipStream_t st);
 
+// The same tail on the block-scaled fp8 matrix cores (mlp_tail_fp8.hip): x
+// (bf16) and the fp32 h2 are MX-quantised inside the kernel (e4m3 + one E8M0
+// byte per 32 columns), W2p / W3p are e4m3 weights in the fragment order of
+// the 16x16x128 MFMA (ops.pack_bfrag_fp8), sw2 / sw3 their per-output-channel
+// fp32 scales. ldx in elements, a multiple of 8; X 16-byte aligned. Same
+// shapes, extra / out_act / y as launch_mlp_tail; act 0 none / 1 relu.
+hipError_t launch_mlp_tail_fp8(const void* X, int64_t ldx, int M, int K1, const void* W2p, const float* sw2,
+                               const float* b2, int act2, int N2, const void* W3p, const float* sw3, const float* b3,
+                               int act3, int N3, const float* hw, float hbias, const float* extra, int extra_n,
+                               int64_t extra_ld, int out_act, float* y, hipStream_t st);
+
 // K1 + K2 + K4 x 3 + K6 (gather_mlp.hip): the DeepFM / Wide&Deep tower in one
 // launch, the resolve pass included: a.table / V / lin / modulo / bias and the
 // rows (a.arena, or a.ids + a.wts) as for launch_embed_resolve, a.B rows, a.F

@@ -58,6 +58,9 @@ class ModelConfig:
     hot_cache_rows: int = -1
     param_dtype: str = "bf16"         # storage dtype of embeddings + dense weights
     gemm_dtype: str = "bf16"          # bf16 | fp8 (dcn_v2 towers on CDNA4 fp8 MFMA)
+    # bf16 | fp8: the last two MLP layers + head as the MX-fp8 fused tail (ops.mlp_tail_fp8);
+    # fp8 needs dcn_v2, gemm_dtype fp8 and mlp_dims ending (1024, 512, 256) - checked when the model is built
+    tail_dtype: str = "bf16"
     seed: int = 1234
 
     @property

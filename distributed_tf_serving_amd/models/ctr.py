@@ -343,13 +343,19 @@ class DCNv2(CTRModel):
                 layer.weight.data.mul_(0.5)
                 if self.fp8:
                     layer.quantize_fp8()
-        self.mlp = MLP(d, cfg.mlp_dims, self.dtype, self.device_, self.gen, fp8=self.fp8)
+        tail_fp8 = cfg.tail_dtype == "fp8"
+        if tail_fp8 and not self.fp8:
+            raise ValueError("tail_dtype: fp8 needs gemm_dtype: fp8")
+        self.mlp = MLP(d, cfg.mlp_dims, self.dtype, self.device_, self.gen, fp8=self.fp8, tail_fp8=tail_fp8)
         # fp8 towers = the cross layers and the first (2752-deep) MLP layer, 97 % of
-        # the FLOPs; the small tail layers stay bf16 so the last layer + head run as
-        # one fused kernel writing the scores to pinned memory (fp8 there needs two
-        # quant passes, a separate head and a D2H copy: 53 us vs ~37 us per
-        # 16384-row step, round 2)
-        if self.fp8:
+        # the FLOPs. By default (tail_dtype: bf16) the small tail layers stay bf16
+        # and run, with the head, as one fused kernel writing the scores to pinned
+        # memory (ops.mlp_tail / ops.linear_head; an fp8 tail made of separate
+        # kernels needs two quant passes, a separate head and a D2H copy: 53 us vs
+        # ~37 us per 16384-row step, round 2). tail_dtype: fp8 (opt-in, preset
+        # dcn_v2_fp8_tail) keeps them fp8: ops.mlp_tail_fp8 quantises its own
+        # operands in-kernel and keeps the fused head.
+        if self.fp8 and not tail_fp8:
             for layer in self.mlp.layers[1:]:
                 layer.fp8 = False
         self.head_wc = nn.Parameter(init_uniform_(torch.empty(d, device=self.device_), 0.5 / math.sqrt(d), self.gen),
@@ -576,6 +582,12 @@ def build_model(cfg: ModelConfig, device="cpu", **kw) -> CTRModel:
         cls = FAMILIES[cfg.family]
     except KeyError:
         raise ValueError(f"unknown model family {cfg.family!r}; known: {sorted(FAMILIES)}") from None
+    if cfg.tail_dtype not in ("bf16", "fp8"):
+        raise ValueError(f"tail_dtype must be bf16 or fp8, got {cfg.tail_dtype!r}")
+    if cfg.tail_dtype == "fp8" and not (cfg.family == "dcn_v2" and cfg.gemm_dtype == "fp8"
+                                        and tuple(cfg.mlp_dims[-3:]) == (1024, 512, 256)):
+        raise ValueError("tail_dtype: fp8 needs family dcn_v2, gemm_dtype fp8 and mlp_dims ending (1024, 512, 256); "
+                         f"got {cfg.family}, {cfg.gemm_dtype}, {tuple(cfg.mlp_dims)}")
     m = cls(cfg, device=device, **kw).eval()
     m.gen = None  # init-only RNG; keeps the module deep-copyable / movable
     return m

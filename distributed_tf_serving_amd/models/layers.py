@@ -116,20 +116,30 @@ class Dense(nn.Module):
         self.register_buffer("w_fp8", q.contiguous(), persistent=False)
         self.register_buffer("w_scale", sw.contiguous(), persistent=False)
         self.fp8 = True
+        self._fp8_gen = self.__dict__.get("_fp8_gen", 0) + 1  # a new w_fp8: packed("16f8") re-packs
 
     def packed(self, layout: str = "16") -> torch.Tensor:
         """The weight in MFMA fragment order - "16": ops.pack_bfrag (the fused
         MLP tail's 16x16x32 B operand), "32": ops.pack_frag32 (the gather-GEMM's
         and the one-launch tower's 32x32x16 A operand) - re-packed whenever the weight changed
         (load_state_dict bumps its version). Built by the eager warm-up that
-        precedes every graph capture."""
-        key = (self.weight.data_ptr(), self.weight._version)
+        precedes every graph capture. "16f8": ops.pack_bfrag_fp8 of ``w_fp8``
+        (the MX-fp8 tail's 16x16x128 B operand), re-packed whenever
+        quantize_fp8() replaced ``w_fp8``."""
+        if layout == "16f8":
+            key = (self.w_fp8.data_ptr(), self._fp8_gen)
+        else:
+            key = (self.weight.data_ptr(), self.weight._version)
         cache = self.__dict__.setdefault("_packed", {})
         cached = cache.get(layout)
         if cached is None or cached[0] != key:
             w = self.weight.detach()
-            fresh = ops.pack_bfrag(w) if layout == "16" else ops.pack_frag32(w)
-            if cached is not None and cached[1].shape == fresh.shape and cached[1].dtype == fresh.dtype:
+            if layout == "16f8":
+                fresh = ops.pack_bfrag_fp8(self.w_fp8)
+            else:
+                fresh = ops.pack_bfrag(w) if layout == "16" else ops.pack_frag32(w)
+            if (cached is not None and cached[1].shape == fresh.shape and cached[1].dtype == fresh.dtype
+                    and cached[1].device == fresh.device):
                 # a weight changed in place: re-pack INTO the buffer captured HIP
                 # graphs already read (a new allocation would leave them serving
                 # the old weights)
@@ -149,9 +159,15 @@ class Dense(nn.Module):
 
 class MLP(nn.Module):
     def __init__(self, in_dim: int, dims: Sequence[int], dtype, device, gen, fp8: bool = False,
-                 last_act: str = "relu", in_pad: Optional[int] = None):
-        """``in_pad``: the first layer's K (>= in_dim, zero weight columns)."""
+                 last_act: str = "relu", in_pad: Optional[int] = None, tail_fp8: bool = False):
+        """``in_pad``: the first layer's K (>= in_dim, zero weight columns).
+        ``tail_fp8``: the last two layers (1024 -> 512 -> 256, fp8) and the head
+        run as ops.mlp_tail_fp8 on every device and row count."""
         super().__init__()
+        if tail_fp8 and not (fp8 and len(dims) >= 2 and (in_dim, *dims)[-3:] == (1024, 512, 256)):
+            raise ValueError(f"tail_fp8 needs fp8 layers ending 1024 -> 512 -> 256, got fp8={fp8}, "
+                             f"dims {(in_dim, *dims)}")
+        self.tail_fp8 = tail_fp8
         layers: List[Dense] = []
         d = in_dim
         for i, h in enumerate(dims):
@@ -181,6 +197,15 @@ class MLP(nn.Module):
         while n - k > 2:  # the layers in front of the tail (DCN-v2: the fp8 first layer)
             x = self.layers[k](x, xq if k == start else None)
             k += 1
+        if self.tail_fp8:
+            # one numerics on every device and row count (CPU: the reference
+            # math of the same contract); never the bf16 tail
+            if n - k != 2 or (xq is not None and k == start) or not ops.mlp_tail_fp8_ok(x, *self.layers[k:]):
+                raise ValueError("fp8 MLP tail: the last two layers must be fp8 1024 -> 512 -> 256 on bf16 rows")
+            l2, l3 = self.layers[k:]
+            w2, w3 = (l2.packed("16f8"), l3.packed("16f8")) if x.is_cuda else (l2.w_fp8, l3.w_fp8)
+            return ops.mlp_tail_fp8(x, w2, l2.w_scale, l2.bias, l2.act, w3, l3.w_scale, l3.bias, l3.act, head_w,
+                                    head_b, extra=extra, sigmoid=sigmoid, out=out)
         if n - k == 2 and x.is_cuda and (xq is None or k > start) and ops.mlp_tail_ok(x, *self.layers[k:]):
             l2, l3 = self.layers[k:]
             return ops.mlp_tail(x, l2.packed(), l2.bias, l2.act, l3.packed(), l3.bias, l3.act, head_w, head_b,

@@ -12,7 +12,7 @@ Every op dispatches on the device of its inputs:
 Op inventory: K0 ``pack_ids``, K1 ``embed``, K1b
 ``embedding_bag``, K2 FM (fused in ``embed``), K3 ``cross_v1``, K3b
 ``cross_v2`` / ``linear_fp8``, K4 ``linear``, K5 ``dot_interaction``, K6
-``head``, K4+K6 ``linear_head``, K7 ``sort_scores``, K7s ``rank_segments`` /
+``head``, K4+K6 ``linear_head``, K4+K4+K6 ``mlp_tail`` / ``mlp_tail_fp8``, K7 ``sort_scores``, K7s ``rank_segments`` /
 ``rank_arena``.
 """
 from __future__ import annotations
@@ -739,6 +739,83 @@ def mlp_tail(x: torch.Tensor, W2p: torch.Tensor, b2: torch.Tensor, act2: str, W3
     ``W2p`` / ``W3p``: :func:`pack_bfrag` of the two weights. ``out`` may be
     pinned host memory (the kernel writes the scores there)."""
     return hip().mlp_tail(x, W2p, b2, _ACTS[act2], W3p, b3, _ACTS[act3], hw, float(hbias), extra, sigmoid, out)
+
+
+def pack_bfrag_fp8(Wq: torch.Tensor) -> torch.Tensor:
+    """e4m3 weights [N, K] -> B-fragment order of v_mfma_scale_f32_16x16x128_f8f6f4
+    (csrc/kernels/mlp_tail_fp8.hip), shape [N / 16, K / 128, 2, 64, 16]: block
+    (n16, k128) is 2 KiB of contiguous bytes, byte e of lane l = 16 fq + fr in
+    half h being
+
+        P[n16, k128, h, 16 fq + fr, e] = Wq[16 n16 + fr, 128 k128 + 64 h + 16 fq + e]
+
+    - the lane's 16-byte K chunks fq and fq + 4 of the 128-deep tile, the
+    operand layout the MFMA reads (gemm.hip mx_frag); flat byte offset
+    ((n16 K/128 + k128) 2 + h) 1024 + 16 l + e. One wave-instruction (16 bytes
+    per lane) reads each 1 KiB half."""
+    if Wq.dim() != 2 or Wq.dtype != torch.float8_e4m3fn:
+        raise ValueError(f"pack_bfrag_fp8 needs e4m3 [N, K], got {Wq.dtype} {tuple(Wq.shape)}")
+    N, K = Wq.shape
+    if N % 16 or K % 128 or N == 0 or K == 0:
+        raise ValueError(f"pack_bfrag_fp8 needs N % 16 == 0 and K % 128 == 0, got {tuple(Wq.shape)}")
+    b = Wq.contiguous().view(torch.uint8).reshape(N // 16, 16, K // 128, 2, 4, 16)  # n16, fr, k128, h, fq, e
+    return b.permute(0, 2, 3, 4, 1, 5).contiguous().reshape(N // 16, K // 128, 2, 64, 16).view(torch.float8_e4m3fn)
+
+
+def unpack_bfrag_fp8(P: torch.Tensor, N: int, K: int) -> torch.Tensor:
+    """Inverse of :func:`pack_bfrag_fp8`: e4m3 [N, K]."""
+    if N % 16 or K % 128 or N <= 0 or K <= 0 or P.numel() != N * K or P.dtype != torch.float8_e4m3fn:
+        raise ValueError(f"unpack_bfrag_fp8 needs e4m3 with N K elements, N % 16 == 0, K % 128 == 0, got "
+                         f"{P.dtype} {tuple(P.shape)} for N = {N}, K = {K}")
+    b = P.contiguous().view(torch.uint8).reshape(N // 16, K // 128, 2, 4, 16, 16)  # n16, k128, h, fq, fr, e
+    return b.permute(0, 4, 1, 2, 3, 5).reshape(N, K).contiguous().view(torch.float8_e4m3fn)
+
+
+def mlp_tail_fp8_ok(x: torch.Tensor, l2, l3) -> bool:
+    """Shapes the MX-fp8 fused tail covers: bf16 [M, 1024] rows -> 512 -> 256 ->
+    score, fp8 layers with ReLU / linear activations; any row count."""
+    return (x.dtype == torch.bfloat16 and x.dim() == 2 and x.stride(1) == 1 and x.shape[1] == 1024
+            and bool(l2.fp8) and bool(l3.fp8) and tuple(l2.w_fp8.shape) == (512, 1024)
+            and tuple(l3.w_fp8.shape) == (256, 512) and l2.act in ("relu", "none") and l3.act in ("relu", "none"))
+
+
+def mlp_tail_fp8(x: torch.Tensor, W2q: torch.Tensor, sw2: torch.Tensor, b2: torch.Tensor, act2: str,
+                 W3q: torch.Tensor, sw3: torch.Tensor, b3: torch.Tensor, act3: str, hw: torch.Tensor,
+                 hbias: float = 0.0, extra: Optional[torch.Tensor] = None, sigmoid: bool = True,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The fused MLP tail on MX-fp8 operands quantised on the fly (1024 -> 512 -> 256 -> score):
+
+        (xq, sx)  = quant_mx_fp8(x)                       x bf16 [M, 1024]
+        h2        = act2(dequant(xq, sx) W2q^T * sw2 + b2)      fp32, not rounded to bf16
+        (h2q, s2) = quant_mx_fp8(h2)
+        h3        = act3(dequant(h2q, s2) W3q^T * sw3 + b3)     fp32
+        y         = out_act(h3 . hw + hbias + extra)            extra / out as in mlp_tail
+
+    ``W2q`` / ``W3q``: e4m3 weights with per-output-channel scales ``sw*``
+    (Dense.w_fp8 / w_scale). GPU: W2q / W3q are their :func:`pack_bfrag_fp8`
+    copies (Dense.packed("16f8")) and one kernel quantises x and h2 itself
+    (csrc/kernels/mlp_tail_fp8.hip). CPU: plain [N, K] weights, reference math."""
+    if act2 not in ("relu", "none") or act3 not in ("relu", "none"):
+        raise ValueError(f"mlp_tail_fp8 activations must be relu or none, got {act2!r}, {act3!r}")
+    if x.is_cuda:
+        return hip().mlp_tail_fp8(x, W2q, sw2, b2, _ACTS[act2], W3q, sw3, b3, _ACTS[act3], hw, float(hbias), extra,
+                                  sigmoid, out)
+    if tuple(x.shape[1:]) != (1024,) or tuple(W2q.shape) != (512, 1024) or tuple(W3q.shape) != (256, 512):
+        raise ValueError("mlp_tail_fp8 covers x [M, 1024], W2q [512, 1024], W3q [256, 512]")
+    h = dequant_mx_fp8(*quant_mx_fp8(x)) @ W2q.float().t() * sw2.float() + b2.float()
+    if act2 == "relu":
+        h = torch.relu(h)
+    h = dequant_mx_fp8(*quant_mx_fp8(h)) @ W3q.float().t() * sw3.float() + b3.float()
+    if act3 == "relu":
+        h = torch.relu(h)
+    y = h @ hw.float() + float(hbias)
+    if extra is not None:
+        y = y + _extra_logit(extra, y.shape[0])
+    y = torch.sigmoid(y) if sigmoid else y
+    if out is not None:
+        out.copy_(y)
+        return out
+    return y
 
 
 # The whole DeepFM / Wide&Deep tower as one kernel (gather_mlp.hip) at or above
