@@ -738,6 +738,116 @@ torch::Tensor dot_interaction_gather_arena(torch::Tensor dense, torch::Tensor ta
   return out;
 }
 
+// ---------------------------------------------------------------- fp8 tables
+// e4m3 codes [V, 64] + one power-of-two fp32 scale per table (interaction_fp8.hip)
+static void check_fp8_table(const torch::Tensor& ref, const torch::Tensor& codes, const torch::Tensor& scale, int64_t T) {
+  check_same_dev(ref, codes, "emb_q");
+  check_same_dev(ref, scale, "emb_scale");
+  TORCH_CHECK(codes.scalar_type() == torch::kFloat8_e4m3fn, "emb_q must be float8_e4m3fn codes");
+  TORCH_CHECK(codes.dim() == 2 && codes.size(1) == 64 && codes.is_contiguous() && codes.size(0) >= 1,
+              "emb_q must be contiguous [V, 64]");
+  TORCH_CHECK(scale.scalar_type() == torch::kFloat32 && scale.dim() == 1 && scale.numel() == T && scale.is_contiguous(),
+              "emb_scale must be fp32 [T], one scale per table");
+}
+
+// ids (int32/int64 [B, T] row view) or a device request arena, as in the bf16 pair above
+static torch::Tensor dot_interaction_gather_fp8_impl(torch::Tensor dense, torch::Tensor codes, torch::Tensor scale,
+                                                     const torch::Tensor* ids, const torch::Tensor* arena,
+                                                     int64_t id_col0, torch::Tensor modulo_f, torch::Tensor offset_f,
+                                                     int64_t out_cols) {
+  check_dev(dense, "dense");
+  TORCH_CHECK(dense.scalar_type() == torch::kBFloat16, "dense must be bf16");
+  TORCH_CHECK(dense.dim() == 2 && dense.size(1) == 64 && dense.stride(1) == 1 && dense.stride(0) % 8 == 0 &&
+                  dense.stride(0) >= 64,
+              "dense must be [B, 64] with unit inner stride");
+  const int64_t B = dense.size(0), T = modulo_f.numel();
+  TORCH_CHECK(T >= 1 && T + 1 <= 32, "dot interaction kernel handles 1 <= T <= 31 tables");
+  check_fp8_table(dense, codes, scale, T);
+  for (auto* t : {&modulo_f, &offset_f}) {
+    check_same_dev(dense, *t, "table map");
+    TORCH_CHECK(t->scalar_type() == torch::kInt64 && t->numel() == T && t->is_contiguous(), "modulo_f / offset_f: int64 [T]");
+  }
+  if (ids) {
+    check_same_dev(dense, *ids, "ids");
+    TORCH_CHECK((ids->scalar_type() == torch::kInt64 || ids->scalar_type() == torch::kInt32) && ids->dim() == 2 &&
+                    ids->stride(1) == 1 && ids->size(0) == B && ids->size(1) == T && ids->stride(0) >= T,
+                "ids must be int32/int64 [B, T] rows with unit inner stride");
+  } else {
+    check_same_dev(dense, *arena, "arena");
+    TORCH_CHECK(arena->scalar_type() == torch::kUInt8 && arena->is_contiguous(), "arena must be a contiguous uint8 buffer");
+    TORCH_CHECK(id_col0 >= 0, "id_col0 >= 0");
+  }
+  const int64_t used = 64 + (T + 1) * T / 2;
+  if (out_cols <= 0) out_cols = (used + 7) / 8 * 8;
+  TORCH_CHECK(out_cols >= used && out_cols % 8 == 0 && out_cols <= 1024, "out_cols: >= used, a multiple of 8, <= 1024");
+  c10::DeviceGuard g(dense.device());
+  auto out = torch::empty({B, out_cols}, dense.options());
+  check_hip(dtfs::launch_dot_interaction_gather_fp8(
+                dense.data_ptr(), dense.stride(0), codes.data_ptr(), codes.size(0), scale.data_ptr<float>(),
+                ids ? ids->data_ptr() : nullptr, ids ? ids->scalar_type() == torch::kInt64 : true,
+                ids ? ids->stride(0) : 0, modulo_f.data_ptr<int64_t>(), offset_f.data_ptr<int64_t>(), int(T), int(B),
+                out.data_ptr(), out_cols, int(out_cols), cur_stream(dense), arena ? arena->data_ptr() : nullptr,
+                int(id_col0)),
+            "dot_interaction_gather_fp8");
+  return out;
+}
+
+torch::Tensor dot_interaction_gather_fp8(torch::Tensor dense, torch::Tensor codes, torch::Tensor scale,
+                                         torch::Tensor ids, torch::Tensor modulo_f, torch::Tensor offset_f,
+                                         int64_t out_cols) {
+  return dot_interaction_gather_fp8_impl(dense, codes, scale, &ids, nullptr, 0, modulo_f, offset_f, out_cols);
+}
+
+torch::Tensor dot_interaction_gather_fp8_arena(torch::Tensor dense, torch::Tensor codes, torch::Tensor scale,
+                                               torch::Tensor arena, int64_t id_col0, torch::Tensor modulo_f,
+                                               torch::Tensor offset_f, int64_t out_cols) {
+  return dot_interaction_gather_fp8_impl(dense, codes, scale, nullptr, &arena, id_col0, modulo_f, offset_f, out_cols);
+}
+
+// K1b on fp8 tables: bag b reads table b % T's scale (scale fp32 [T])
+torch::Tensor embedding_bag_fp8(torch::Tensor codes, torch::Tensor scale, torch::Tensor idx, torch::Tensor offsets,
+                                c10::optional<torch::Tensor> psw, int64_t modulo, bool mean, bool out_bf16,
+                                c10::optional<torch::Tensor> out_opt) {
+  check_dev(codes, "emb_q");
+  check_same_dev(codes, idx, "indices");
+  check_same_dev(codes, offsets, "offsets");
+  TORCH_CHECK(scale.dim() == 1 && scale.numel() >= 1, "emb_scale must be fp32 [T], T >= 1");
+  check_fp8_table(codes, codes, scale, scale.numel());
+  TORCH_CHECK(idx.dim() == 1 && idx.is_contiguous() &&
+                  (idx.scalar_type() == torch::kInt64 || idx.scalar_type() == torch::kInt32),
+              "indices must be contiguous int32/int64 [nnz]");
+  TORCH_CHECK(offsets.dim() == 1 && offsets.scalar_type() == torch::kInt64 && offsets.numel() >= 1 &&
+                  offsets.is_contiguous(),
+              "offsets must be contiguous int64 [nbags+1]");
+  const int64_t D = 64, R = codes.size(0), nbags = offsets.numel() - 1;
+  TORCH_CHECK(modulo > 0 && modulo <= R, "modulo must be in (0, rows]");
+  // offsets are clamped into [0, nnz] inside the kernel (no host sync here)
+  if (psw) {
+    check_same_dev(codes, *psw, "per_sample_weights");
+    TORCH_CHECK(psw->scalar_type() == torch::kFloat32 && psw->numel() == idx.numel() && psw->is_contiguous(),
+                "per_sample_weights: contiguous fp32 [nnz]");
+  }
+  c10::DeviceGuard g(codes.device());
+  const auto odt = out_bf16 ? torch::kBFloat16 : torch::kFloat32;
+  torch::Tensor out;
+  if (out_opt) {  // a static buffer (captured steps)
+    check_same_dev(codes, *out_opt, "out");
+    TORCH_CHECK(out_opt->scalar_type() == odt && out_opt->is_contiguous() && out_opt->numel() == nbags * D,
+                "out must be contiguous [nbags, 64] of the output dtype");
+    out = *out_opt;
+  } else {
+    out = torch::empty({nbags, D}, codes.options().dtype(odt));
+  }
+  check_hip(dtfs::launch_embedding_bag_fp8(codes.data_ptr(), R, scale.data_ptr<float>(), int(scale.numel()),
+                                           idx.data_ptr(), idx.scalar_type() == torch::kInt64,
+                                           offsets.data_ptr<int64_t>(), psw ? psw->data_ptr<float>() : nullptr,
+                                           int(nbags), idx.numel(), modulo, mean,
+                                           out_bf16 ? nullptr : out.data_ptr<float>(),
+                                           out_bf16 ? out.data_ptr() : nullptr, D, cur_stream(codes)),
+            "embedding_bag_fp8");
+  return out;
+}
+
 // ---------------------------------------------------------------- K1b routing
 torch::Tensor shard_route(c10::optional<torch::Tensor> ids, c10::optional<torch::Tensor> arena, int64_t B, int64_t F,
                           int64_t W, int64_t tm, torch::Tensor col, torch::Tensor mod, torch::Tensor off,
@@ -1947,6 +2057,16 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("b1"), py::arg("W2"), py::arg("b2"), py::arg("W3"), py::arg("b3"));
   m.def("dot_interaction_gather_arena", &dot_interaction_gather_arena, py::arg("dense"), py::arg("table"),
         py::arg("arena"), py::arg("id_col0"), py::arg("modulo_f"), py::arg("offset_f"), py::arg("out_cols") = 0);
+  m.def("dot_interaction_gather_fp8", &dot_interaction_gather_fp8, py::arg("dense"), py::arg("emb_q"),
+        py::arg("emb_scale"), py::arg("ids"), py::arg("modulo_f"), py::arg("offset_f"), py::arg("out_cols") = 0,
+        "K1 + K5 on fp8 tables: e4m3 codes [V, 64] + one power-of-two scale per table (interaction_fp8.hip)");
+  m.def("dot_interaction_gather_fp8_arena", &dot_interaction_gather_fp8_arena, py::arg("dense"), py::arg("emb_q"),
+        py::arg("emb_scale"), py::arg("arena"), py::arg("id_col0"), py::arg("modulo_f"), py::arg("offset_f"),
+        py::arg("out_cols") = 0);
+  m.def("embedding_bag_fp8", &embedding_bag_fp8, py::arg("emb_q"), py::arg("emb_scale"), py::arg("indices"),
+        py::arg("offsets"), py::arg("per_sample_weights") = py::none(), py::arg("modulo") = 0, py::arg("mean") = false,
+        py::arg("out_bf16") = false, py::arg("out") = py::none(),
+        "K1b on fp8 tables: bag b takes emb_scale[b % T]");
   m.def("cross_gemm_fp8", &cross_gemm_fp8, py::arg("q"), py::arg("sx"), py::arg("Wq"), py::arg("sw"), py::arg("bias"),
         py::arg("x0"), py::arg("xl"), py::arg("want_z") = true, py::arg("head_w") = py::none());
   m.def("cross_combine", &cross_combine, py::arg("y"), py::arg("x0"), py::arg("xl"), py::arg("want_z") = true,

@@ -297,6 +297,23 @@ hipError_t launch_dot_interaction_gather(const void* dense, int64_t ldd, const v
                                          hipStream_t st, const void* arena = nullptr, int id_col0 = 0,
                                          const PeerLookupArgs* peer = nullptr);
 
+// K1 + K5 on fp8 tables (interaction_fp8.hip): the same step with table rows
+// stored as e4m3 codes [table_rows][64] and one power-of-two fp32 scale per
+// table, value = float(code) * scale[t]; bit-equal to the bf16 kernel on the
+// dequantised table. Local tables only (no peer lookup).
+hipError_t launch_dot_interaction_gather_fp8(const void* dense, int64_t ldd, const void* codes, int64_t table_rows,
+                                             const float* scale, const void* ids, bool ids64, int64_t ldi,
+                                             const int64_t* modulo_f, const int64_t* offset_f, int T, int B, void* out,
+                                             int64_t ldo, int out_cols, hipStream_t st, const void* arena = nullptr,
+                                             int id_col0 = 0);
+
+// K1b on fp8 tables (D = 64): launch_embedding_bag with e4m3 codes; bag b
+// takes scale[b % T] (bags laid out [B][T]). modulo in [1, table_rows].
+hipError_t launch_embedding_bag_fp8(const void* codes, int64_t table_rows, const float* scale, int T, const void* idx,
+                                    bool idx64, const int64_t* offsets, const float* psw, int nbags, int64_t nnz,
+                                    int64_t modulo, bool mean, float* out_f32, void* out_bf16, int64_t out_stride,
+                                    hipStream_t st);
+
 // K1b through the peer lookup: out[b][t] (bf16 [B][T][64]) = sum_j w(b, c) *
 // row(t, id(b, c)), c = col0 + t * hot + j (ids / wts [B][F] row views, or
 // the features of a device request arena row).

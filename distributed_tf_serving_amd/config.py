@@ -61,6 +61,9 @@ class ModelConfig:
     # bf16 | fp8: the last two MLP layers + head as the MX-fp8 fused tail (ops.mlp_tail_fp8);
     # fp8 needs dcn_v2, gemm_dtype fp8 and mlp_dims ending (1024, 512, 256) - checked when the model is built
     tail_dtype: str = "bf16"
+    # bf16 | fp8: dlrm tables stored as e4m3 codes (64-byte rows) + one power-of-two scale per table
+    # (csrc/kernels/interaction_fp8.hip); single rank, family dlrm only - checked when the model is built
+    table_dtype: str = "bf16"
     seed: int = 1234
 
     @property

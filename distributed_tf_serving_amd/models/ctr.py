@@ -453,7 +453,8 @@ class DLRM(CTRModel):
 
     family = "dlrm"
 
-    def __init__(self, cfg: ModelConfig, device="cpu", materialize_tables: bool = True):
+    def __init__(self, cfg: ModelConfig, device="cpu", materialize_tables: bool = True,
+                 table_chunk_rows: int = 1 << 19):
         super().__init__(cfg, device)
         D, T = cfg.embed_dim, cfg.num_sparse
         assert D == 64, "DLRM dot-interaction kernel is built for D = 64"
@@ -480,7 +481,15 @@ class DLRM(CTRModel):
         self.register_buffer("col_mod", self.modulo_f.repeat_interleave(self.hot), persistent=False)
         self.register_buffer("col_off", self.offset_f.repeat_interleave(self.hot), persistent=False)
         self.emb = None
-        if materialize_tables:
+        # table_dtype: fp8 - the tables are e4m3 codes emb_q [T * rows, 64] + one
+        # power-of-two scale per table emb_scale [T] (ops "fp8 tables"); emb stays None
+        self.table_fp8 = cfg.table_dtype == "fp8"
+        self.register_buffer("emb_q", None)  # persistent once filled: the store lands in state_dict
+        self.register_buffer("emb_scale", None)
+        if self.table_fp8:
+            if materialize_tables:
+                self._init_fp8_tables(table_chunk_rows)
+        elif materialize_tables:
             t = torch.empty(T * rows, D, dtype=self.dtype, device=self.device_)
             for f in range(T):  # per-table hashed init: shards built elsewhere match these rows exactly
                 hashed_uniform_rows_(t[f * rows:(f + 1) * rows], f, 0, cfg.seed, self.table_bound)
@@ -489,6 +498,67 @@ class DLRM(CTRModel):
     @property
     def table_bound(self) -> float:
         return 1.0 / math.sqrt(self.cfg.embed_dim)
+
+    # -- fp8 tables ----------------------------------------------------------
+    def _alloc_fp8_tables(self) -> None:
+        T, rows, D = self.T, self.cfg.table_rows, self.cfg.embed_dim
+        if self.emb_q is None:
+            self.emb_q = torch.empty(T * rows, D, dtype=torch.float8_e4m3fn, device=self.device_)
+            self.emb_scale = torch.ones(T, dtype=torch.float32, device=self.device_)
+
+    def _init_fp8_tables(self, chunk_rows: int) -> None:
+        """The hashed init of the bf16 tables, quantised chunk by chunk: each
+        chunk goes through a bf16 scratch of at most ``chunk_rows`` (<= 2^19)
+        rows, so the full bf16 table never exists. amax_t := table_bound, the
+        init's bound: the scales are known up front and are the same for any
+        row range of a table."""
+        T, rows, D = self.T, self.cfg.table_rows, self.cfg.embed_dim
+        chunk = max(1, min(int(chunk_rows), 1 << 19, rows))
+        self._alloc_fp8_tables()
+        scale = ops.table_scale_fp8(torch.full((T,), self.table_bound))
+        self.emb_scale.copy_(scale)
+        scratch = torch.empty(chunk, D, dtype=self.dtype, device=self.device_)
+        for f in range(T):
+            s = float(scale[f])
+            for r0 in range(0, rows, chunk):
+                n = min(chunk, rows - r0)
+                hashed_uniform_rows_(scratch[:n], f, r0, self.cfg.seed, self.table_bound)
+                self.emb_q[f * rows + r0:f * rows + r0 + n] = ops.quant_table_fp8(scratch[:n], s)
+
+    @torch.no_grad()
+    def quantize_tables_(self, table: torch.Tensor, chunk_rows: int = 1 << 19) -> "DLRM":
+        """Import a bf16 [T * rows, 64] table (any device) into the fp8 store:
+        per-table scales from the measured amax, rows quantised chunk by chunk
+        (in place: steps captured earlier keep reading the same buffers)."""
+        T, rows, D = self.T, self.cfg.table_rows, self.cfg.embed_dim
+        if not self.table_fp8:
+            raise ValueError("quantize_tables_ needs table_dtype: fp8")
+        if tuple(table.shape) != (T * rows, D):
+            raise ValueError(f"table must be [{T * rows}, {D}], got {tuple(table.shape)}")
+        chunk = max(1, int(chunk_rows))
+        self._alloc_fp8_tables()
+        amax = torch.zeros(T, dtype=torch.float32)
+        for f in range(T):
+            for r0 in range(f * rows, (f + 1) * rows, chunk):
+                part = table[r0:min(r0 + chunk, (f + 1) * rows)]
+                amax[f] = max(float(amax[f]), float(part.abs().max()))
+        scale = ops.table_scale_fp8(amax)
+        self.emb_scale.copy_(scale)
+        for f in range(T):
+            s = float(scale[f])
+            for r0 in range(f * rows, (f + 1) * rows, chunk):
+                r1 = min(r0 + chunk, (f + 1) * rows)
+                self.emb_q[r0:r1] = ops.quant_table_fp8(table[r0:r1].to(self.emb_q.device), s)
+        return self
+
+    def dequant_rows(self, global_rows: torch.Tensor) -> torch.Tensor:
+        """fp32 [n, 64] values of rows of the fp8 store (global row indices into emb_q)."""
+        g = global_rows.reshape(-1).long().to(self.emb_q.device)
+        return ops.dequant_table_fp8(self.emb_q, self.emb_scale, g, torch.div(g, self.cfg.table_rows, rounding_mode="floor"))
+
+    def dequant_table(self) -> torch.Tensor:
+        """The whole store as the bf16 table a ``table_dtype: bf16`` model would hold (exact; small models, tests)."""
+        return self.dequant_rows(torch.arange(self.emb_q.shape[0])).to(self.dtype)
 
     def dense_input(self, wts: torch.Tensor) -> torch.Tensor:
         """Dense features (the first num_dense weight columns) as the bottom
@@ -512,6 +582,8 @@ class DLRM(CTRModel):
         each table's ``hot`` rows weighted by their feat_wts."""
         B = ids.shape[0]
         sp = self.sparse_ids(ids)
+        if self.table_fp8:
+            return self._lookup_fp8(sp, wts, B)
         if self.hot == 1:
             x, _ = ops.embed(self.emb, sp, None, modulo_f=self.modulo_f, offset_f=self.offset_f, want_x=True)
             return x.view(B, self.T, self.cfg.embed_dim)
@@ -522,6 +594,27 @@ class DLRM(CTRModel):
         offsets = torch.arange(0, B * self.T * self.hot + 1, self.hot, dtype=torch.int64, device=rows.device)
         pooled = ops.embedding_bag(self.emb, rows.view(-1), offsets, per_sample_weights=w, out_bf16=True)
         return pooled.view(B, self.T, self.cfg.embed_dim)
+
+    def _lookup_fp8(self, sp: torch.Tensor, wts: Optional[torch.Tensor], B: int) -> torch.Tensor:
+        """lookup() on the fp8 store. One-hot (off the served path, which takes
+        the fused kernel): torch indexing + dequantisation. Multi-hot: the fp8
+        bag kernel, bag (b, t) scaled by table t's scale."""
+        D = self.cfg.embed_dim
+        if self.hot == 1:
+            rows = (self.offset_f.view(1, -1) + torch.remainder(sp.long(), self.modulo_f.view(1, -1)))
+            tables = torch.arange(self.T, device=rows.device).view(1, -1).expand_as(rows)
+            return ops.dequant_table_fp8(self.emb_q, self.emb_scale, rows, tables).to(self.dtype)
+        if self.emb_q.shape[0] < (1 << 31):
+            rows = ops.pack_ids(sp, modulo_f=self.col_mod, offset_f=self.col_off)  # int32 [B, T*hot]
+        else:  # a store past 2^31 rows (30 x 100M): int64 rows
+            rows = (self.col_off.view(1, -1) + torch.remainder(sp.long(), self.col_mod.view(1, -1))).contiguous()
+        w = None
+        if wts is not None:
+            w = wts[:, self.cfg.num_dense:].float().contiguous().view(-1)
+        offsets = torch.arange(0, B * self.T * self.hot + 1, self.hot, dtype=torch.int64, device=rows.device)
+        pooled = ops.embedding_bag_fp8(self.emb_q, self.emb_scale, rows.view(-1), offsets, per_sample_weights=w,
+                                       out_bf16=True)
+        return pooled.view(B, self.T, D)
 
     def interact_and_top(self, dense_out: torch.Tensor, emb: torch.Tensor, out=None) -> torch.Tensor:
         z = ops.dot_interaction(dense_out, emb, self.inter_cols)
@@ -554,7 +647,7 @@ class DLRM(CTRModel):
         """One-hot, local tables, the fused bottom tower: the step reads the
         request arena itself (no unpack pass: K0 fused into the bottom MLP
         and the interaction's gather)."""
-        return self.hot == 1 and self.emb is not None and self._bottom_fused()
+        return self.hot == 1 and (self.emb is not None or self.emb_q is not None) and self._bottom_fused()
 
     # (no resolve lane: step k+1's bottom MLP + gathered interaction on the
     # aux lane beside step k's top MLP measured slower, 100.2 / 100.5 vs
@@ -569,6 +662,12 @@ class DLRM(CTRModel):
             # itself (no [B, T, 64] embedding round trip through HBM)
             z = ops.dot_interaction_gather(dense_out, self.emb, ids if arena else self.sparse_ids(ids), self.modulo_f,
                                            self.offset_f, self.inter_cols, id_col0=self.cfg.num_dense)
+            return self.top.forward_head(z, self.head_w, self.head_b, out=out)
+        if self.hot == 1 and self.emb_q is not None and (arena or ids.is_cuda):
+            # the same one-kernel step on the fp8 store (interaction_fp8.hip)
+            z = ops.dot_interaction_gather_fp8(dense_out, self.emb_q, self.emb_scale,
+                                               ids if arena else self.sparse_ids(ids), self.modulo_f, self.offset_f,
+                                               self.inter_cols, id_col0=self.cfg.num_dense)
             return self.top.forward_head(z, self.head_w, self.head_b, out=out)
         emb = self.lookup(ids, wts)
         return self.interact_and_top(dense_out, emb, out=out)
@@ -588,6 +687,10 @@ def build_model(cfg: ModelConfig, device="cpu", **kw) -> CTRModel:
                                         and tuple(cfg.mlp_dims[-3:]) == (1024, 512, 256)):
         raise ValueError("tail_dtype: fp8 needs family dcn_v2, gemm_dtype fp8 and mlp_dims ending (1024, 512, 256); "
                          f"got {cfg.family}, {cfg.gemm_dtype}, {tuple(cfg.mlp_dims)}")
+    if cfg.table_dtype not in ("bf16", "fp8"):
+        raise ValueError(f"table_dtype must be bf16 or fp8, got {cfg.table_dtype!r}")
+    if cfg.table_dtype == "fp8" and cfg.family != "dlrm":
+        raise ValueError(f"table_dtype: fp8 needs family dlrm (per-table scales); got {cfg.family}")
     m = cls(cfg, device=device, **kw).eval()
     m.gen = None  # init-only RNG; keeps the module deep-copyable / movable
     return m

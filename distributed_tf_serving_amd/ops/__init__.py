@@ -13,7 +13,8 @@ Op inventory: K0 ``pack_ids``, K1 ``embed``, K1b
 ``embedding_bag``, K2 FM (fused in ``embed``), K3 ``cross_v1``, K3b
 ``cross_v2`` / ``linear_fp8``, K4 ``linear``, K5 ``dot_interaction``, K6
 ``head``, K4+K6 ``linear_head``, K4+K4+K6 ``mlp_tail`` / ``mlp_tail_fp8``, K7 ``sort_scores``, K7s ``rank_segments`` /
-``rank_arena``.
+``rank_arena``; on fp8 tables K1+K5 ``dot_interaction_gather_fp8`` and K1b
+``embedding_bag_fp8``.
 """
 from __future__ import annotations
 
@@ -539,6 +540,77 @@ def dot_interaction_gather(dense: torch.Tensor, table: torch.Tensor, ids, modulo
         return hip().dot_interaction_gather(dense, table, _rows(ids), modulo_f, offset_f, int(out_cols))
     rows = _hash_rows(ids, 0, modulo_f, offset_f).clamp(0, table.shape[0] - 1)
     return dot_interaction(dense, table[rows], out_cols)
+
+
+# ------------------------------------------------------------------ fp8 tables
+# DLRM tables stored as OCP e4m3 codes [T * rows, 64] with one fp32 scale per
+# table that is an exact power of two 2^e_t, e_t = _mx_exponent(amax_t):
+# value(t, r, c) = float(code) * scale[t]. Every such value is exactly a bf16
+# value, so an fp8-table model computes bit for bit what a bf16 model holding
+# the dequantised table computes (csrc/kernels/interaction_fp8.hip).
+def table_scale_fp8(amax: torch.Tensor) -> torch.Tensor:
+    """Per-table scale 2^e, e the smallest integer with amax / 2^e <= 448 (1 for an all-zero table)."""
+    return torch.exp2(_mx_exponent(amax.float()).float())
+
+
+def quant_table_fp8(x: torch.Tensor, scale) -> torch.Tensor:
+    """Rows of one table -> e4m3 codes, ``scale`` its power-of-two scale (a float or a 0-dim tensor)."""
+    return (x.float() * (1.0 / scale)).clamp(-FP8_MAX, FP8_MAX).to(torch.float8_e4m3fn)
+
+
+def dequant_table_fp8(emb_q: torch.Tensor, emb_scale: torch.Tensor, rows: torch.Tensor,
+                      tables: torch.Tensor) -> torch.Tensor:
+    """fp32 [..., 64] values of the code rows ``rows`` (global row indices), row i belonging to table ``tables[i]``."""
+    codes = emb_q.view(torch.uint8)[rows].view(torch.float8_e4m3fn)
+    return codes.float() * emb_scale[tables].unsqueeze(-1)
+
+
+def dot_interaction_gather_fp8(dense: torch.Tensor, emb_q: torch.Tensor, emb_scale: torch.Tensor, ids,
+                               modulo_f: torch.Tensor, offset_f: torch.Tensor, out_cols: int = 0,
+                               id_col0: int = 0) -> torch.Tensor:
+    """:func:`dot_interaction_gather` on fp8 tables: ``emb_q`` float8_e4m3fn
+    [V, 64] codes, ``emb_scale`` fp32 [T]. ``ids`` as there (int32/int64 [B, T]
+    rows or :class:`ArenaRows`). CPU: fp32 math on the dequantised rows."""
+    T = int(modulo_f.numel())
+    if out_cols <= 0:
+        out_cols = interaction_cols(T, dense.shape[1])
+    if isinstance(ids, ArenaRows):
+        if ids.arena.is_cuda:
+            return hip().dot_interaction_gather_fp8_arena(dense, emb_q, emb_scale, ids.arena, int(id_col0), modulo_f,
+                                                          offset_f, int(out_cols))
+        ids = _arena_unpack_host(ids)[0][:, id_col0:id_col0 + T]
+    if dense.is_cuda:
+        return hip().dot_interaction_gather_fp8(dense, emb_q, emb_scale, _rows(ids), modulo_f, offset_f, int(out_cols))
+    rows = _hash_rows(ids, 0, modulo_f, offset_f).clamp(0, emb_q.shape[0] - 1)
+    tables = torch.arange(T).view(1, T).expand_as(rows)
+    return dot_interaction(dense, dequant_table_fp8(emb_q, emb_scale, rows, tables), out_cols)
+
+
+def embedding_bag_fp8(emb_q: torch.Tensor, emb_scale: torch.Tensor, indices: torch.Tensor, offsets: torch.Tensor,
+                      per_sample_weights: Optional[torch.Tensor] = None, modulo: int = 0, mean: bool = False,
+                      out_bf16: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """:func:`embedding_bag` on fp8 tables: bag b belongs to table b mod T
+    (bags laid out [B, T], as DLRM.lookup builds them) and takes
+    ``emb_scale[b mod T]``. CPU: fp32 math on the dequantised rows."""
+    if emb_q.is_cuda:
+        m = int(modulo) if modulo > 0 else emb_q.shape[0]
+        return hip().embedding_bag_fp8(emb_q, emb_scale, indices.contiguous(), offsets.contiguous(),
+                                       per_sample_weights, m, mean, out_bf16, out)
+    if mean and per_sample_weights is not None:
+        raise ValueError("per_sample_weights with mean pooling is not supported")
+    T, nnz, nbags = int(emb_scale.numel()), int(indices.numel()), int(offsets.numel()) - 1
+    rows = _hash_rows(indices, modulo if modulo > 0 else emb_q.shape[0])
+    bounds = offsets.clamp(0, nnz)
+    bag = torch.searchsorted(bounds[1:].contiguous(), torch.arange(nnz), right=True).clamp(max=max(nbags - 1, 0))
+    vals = dequant_table_fp8(emb_q, emb_scale, rows, torch.remainder(bag, T))  # [nnz, 64]: the rows the bags read
+    res = torch.nn.functional.embedding_bag(torch.arange(nnz), vals, offsets[:-1], mode="mean" if mean else "sum",
+                                            per_sample_weights=None if mean else per_sample_weights,
+                                            include_last_offset=False)
+    res = res.to(torch.bfloat16) if out_bf16 else res
+    if out is not None:
+        out.copy_(res.view(out.shape))
+        return out
+    return res
 
 
 def dot_interaction_gather_peer(dense: torch.Tensor, ids, peer, cache=None, out_cols: int = 0,

@@ -459,6 +459,12 @@ def peer_access_everywhere(ctx: DistContext, device: torch.device, group=None) -
     return all(votes)
 
 
+def _reject_fp8_tables(cfg: ModelConfig) -> None:
+    if getattr(cfg, "table_dtype", "bf16") != "bf16":
+        raise ValueError(f"table_dtype: {cfg.table_dtype} tables are single-rank only: the sharded and peer "
+                         "lookups read bf16 rows (serve the model unsharded, or use table_dtype: bf16)")
+
+
 def build_parallel_model(cfg: ModelConfig, device, ctx: Optional[DistContext] = None, shard_tables: str = "auto",
                          policy: str = "auto", budget_bytes: int = int(0.8 * MI355X_HBM_BYTES), group=None):
     """The model a rank serves: DLRM tables are sharded across the process
@@ -469,6 +475,7 @@ def build_parallel_model(cfg: ModelConfig, device, ctx: Optional[DistContext] = 
 
     ctx = ctx or DistContext(device=torch.device(device))
     if cfg.family == "dlrm" and (shard_tables == "on" or (shard_tables == "auto" and ctx.is_distributed)):
+        _reject_fp8_tables(cfg)
         return ShardedDLRM(cfg, ctx, device=device, policy=policy, budget_bytes=budget_bytes, group=group).eval()
     return build_model(cfg, device)
 
@@ -488,6 +495,7 @@ class ShardedDLRM(nn.Module):
     def __init__(self, cfg: ModelConfig, ctx: DistContext, device="cpu", plan: Optional[ShardingPlan] = None,
                  policy: str = "auto", budget_bytes: int = int(0.8 * MI355X_HBM_BYTES), group=None):
         super().__init__()
+        _reject_fp8_tables(cfg)
         self.cfg, self.ctx, self.group = cfg, ctx, group
         self.hot = max(1, int(getattr(cfg, "multi_hot", 1)))
         world = ctx.world if ctx.is_distributed else 1

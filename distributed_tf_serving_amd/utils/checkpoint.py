@@ -67,6 +67,12 @@ def read_config(path: str) -> ModelConfig:
 
 
 # ---------------------------------------------------------------- sharded DLRM
+def _bf16_tables_only(cfg: ModelConfig) -> None:
+    # fp8 tables (table_dtype: fp8) are single-rank: save_model / load_model round-trip emb_q + emb_scale
+    if getattr(cfg, "table_dtype", "bf16") != "bf16":
+        raise ValueError("sharded checkpoints hold bf16 table rows; use save_model / load_model for fp8 tables")
+
+
 def _shard_key(table: int, lo: int) -> str:
     return f"table{table}.rows{lo}"
 
@@ -75,6 +81,7 @@ def save_sharded(model, path: str) -> None:
     """Collective over the model's process group: every rank writes its file."""
     import torch.distributed as dist
 
+    _bf16_tables_only(model.cfg)
     emb = model.emb
     rank, world = emb.rank, emb.world
     os.makedirs(path, exist_ok=True)
@@ -104,8 +111,11 @@ def save_sharded(model, path: str) -> None:
 
 def load_sharded(model, path: str) -> None:
     """Fill this rank's shards (any saved world size) and the dense towers."""
+    _bf16_tables_only(model.cfg)
     with open(os.path.join(path, MANIFEST)) as f:
         manifest = json.load(f)
+    if manifest.get("model_config", {}).get("table_dtype", "bf16") != "bf16":
+        raise ValueError("sharded checkpoints hold bf16 table rows; this one was written with fp8 tables")
     by_table: Dict[int, List[dict]] = {}
     for s in manifest["shards"]:
         by_table.setdefault(s["table"], []).append(s)
