@@ -1632,6 +1632,80 @@ void rank_arena(torch::Tensor arena, torch::Tensor scores, torch::Tensor out_val
             "rank_arena");
 }
 
+// ---------------------------------------------------------------- K7t
+void topk_segments(torch::Tensor s, torch::Tensor offsets, torch::Tensor k, torch::Tensor out_vals,
+                   torch::Tensor out_idx) {
+  check_rank_buf(s, torch::kFloat32, "scores");
+  check_rank_buf(out_vals, torch::kFloat32, "out_vals");
+  check_rank_buf(out_idx, torch::kInt64, "out_idx");
+  TORCH_CHECK(offsets.dim() == 1 && offsets.numel() >= 1 &&
+                  (offsets.scalar_type() == torch::kInt32 || offsets.scalar_type() == torch::kInt64),
+              "offsets must be int32/int64 [S + 1]");
+  const int64_t N = s.numel(), S = offsets.numel() - 1;
+  TORCH_CHECK(k.dim() == 1 && (k.scalar_type() == torch::kInt32 || k.scalar_type() == torch::kInt64),
+              "k must be an int32/int64 [S] tensor");
+  if (k.numel() != S) throw py::value_error("topk_segments: k must hold one entry per segment (" + std::to_string(S) + ")");
+  if (out_vals.numel() != N || out_idx.numel() != N)
+    throw py::value_error("topk_segments: out_vals / out_idx must be as long as the " + std::to_string(N) + " scores");
+  const torch::Tensor oh = offsets.to(torch::kCPU, torch::kInt64).contiguous();
+  const torch::Tensor kh = k.to(torch::kCPU, torch::kInt64).contiguous();
+  const int64_t* o = oh.data_ptr<int64_t>();
+  const int64_t* kp = kh.data_ptr<int64_t>();
+  int64_t max_len = 0;
+  bool any = false;
+  if (o[0] < 0) throw py::value_error("topk_segments: offsets must not be negative");
+  for (int64_t i = 0; i < S; ++i) {
+    if (o[i + 1] < o[i]) throw py::value_error("topk_segments: offsets must be ascending");
+    if (kp[i] < 0) throw py::value_error("topk_segments: k must not be negative");
+    max_len = std::max(max_len, o[i + 1] - o[i]);
+    any = any || (kp[i] > 0 && o[i + 1] > o[i]);
+  }
+  if (o[S] > N) throw py::value_error("topk_segments: offsets run past the " + std::to_string(N) + " scores");
+  if (max_len > dtfs::rank_max_elems())
+    throw py::value_error("topk_segments: a segment has " + std::to_string(max_len) +
+                          " scores; the kernel takes at most " + std::to_string(dtfs::rank_max_elems()));
+  // the launch runs on the device that holds a device buffer (pinned ones are mapped on every device)
+  c10::Device dev(c10::DeviceType::CUDA, c10::hip::current_device());
+  bool have = false;
+  for (const auto* t : {&s, &out_vals, &out_idx}) {
+    if (!t->is_cuda()) continue;
+    TORCH_CHECK(!have || t->device() == dev, "topk_segments: device buffers must share one device");
+    dev = t->device();
+    have = true;
+  }
+  if (!any) return;
+  c10::DeviceGuard g(dev);
+  const int64_t kcap = dtfs::rank_max_elems();
+  // offsets and k in one copy: [S + 1] offsets, then [S] k
+  torch::Tensor both = torch::empty({2 * S + 1}, torch::dtype(torch::kInt32));
+  int32_t* bp = both.data_ptr<int32_t>();
+  for (int64_t i = 0; i <= S; ++i) bp[i] = int32_t(o[i]);
+  for (int64_t i = 0; i < S; ++i) bp[S + 1 + i] = int32_t(std::min(kp[i], kcap));
+  const torch::Tensor bd = both.to(dev);
+  const int32_t* od = bd.data_ptr<int32_t>();
+  check_hip(dtfs::launch_topk_segments(s.data_ptr<float>(), N, od, od + S + 1, int(S),
+                                       int(max_len), out_vals.data_ptr<float>(), out_idx.data_ptr<int64_t>(),
+                                       c10::hip::getCurrentHIPStream(dev.index()).stream()),
+            "topk_segments");
+}
+
+void topk_arena(torch::Tensor arena, torch::Tensor scores, torch::Tensor out_vals, torch::Tensor out_idx) {
+  check_dev(arena, "arena");
+  TORCH_CHECK(arena.scalar_type() == torch::kUInt8 && arena.numel() > dtfs::kArenaPayloadOff, "arena: uint8 [cap]");
+  check_rank_buf(scores, torch::kFloat32, "scores");
+  check_rank_buf(out_vals, torch::kFloat32, "out_vals");
+  check_rank_buf(out_idx, torch::kInt64, "out_idx");
+  const int64_t n = scores.numel();
+  TORCH_CHECK(out_vals.numel() >= n && out_idx.numel() >= n, "out_vals / out_idx must hold the ", n, " scores");
+  for (const auto* t : {&scores, &out_vals, &out_idx})
+    TORCH_CHECK(!t->is_cuda() || t->device() == arena.device(), "topk_arena: buffers must be on ", arena.device());
+  c10::DeviceGuard g(arena.device());
+  // the kernel checks every descriptor against n before it reads or writes
+  check_hip(dtfs::launch_topk_arena(arena.data_ptr(), scores.data_ptr<float>(), n, out_vals.data_ptr<float>(),
+                                    out_idx.data_ptr<int64_t>(), cur_stream(arena)),
+            "topk_arena");
+}
+
 // ---------------------------------------------------------------- fan-out step
 // Validates the device/host buffers of one fan-out step (everything but the
 // per-step H2D source) and computes the per-peer message sizes.
@@ -2100,6 +2174,11 @@ PYBIND11_MODULE(_hip, m) {
   m.def("rank_segments", &rank_segments, py::arg("scores"), py::arg("offsets"), py::arg("descending") = false,
         py::arg("k") = -1, py::arg("out_vals") = py::none(), py::arg("out_idx") = py::none());
   m.def("rank_arena", &rank_arena, py::arg("arena"), py::arg("scores"), py::arg("out_vals"), py::arg("out_idx"));
+  m.def("topk_select_max", &dtfs::topk_select_max);
+  m.def("topk_select_min", &dtfs::topk_select_min);
+  m.def("topk_segments", &topk_segments, py::arg("scores"), py::arg("offsets"), py::arg("k"), py::arg("out_vals"),
+        py::arg("out_idx"));
+  m.def("topk_arena", &topk_arena, py::arg("arena"), py::arg("scores"), py::arg("out_vals"), py::arg("out_idx"));
   m.def("sort_max_elems", &dtfs::sort_max_elems);
 
   py::class_<dtfs::runtime::StepRunner>(m, "StepRunner",

@@ -88,7 +88,9 @@ __device__ __forceinline__ uint32_t load_u32_unaligned(const uint8_t* p) {
 }
 
 // Request-arena header (csrc/runtime/arena.h): n_req @0, total_rows @8,
-// row_table_off @16 ({ids_off, wts_off} int32 per row, payload-relative).
+// row_table_off @16 ({ids_off, wts_off} int32 per row, payload-relative);
+// n_ranked @44 (rank.hip), n_topk @48 and topk_table_off @56 (int32 k per
+// descriptor, payload-relative; topk.hip).
 // A row whose ids_off has bit 31 set was narrowed by the host while it copied
 // the request (runtime/narrow.h): int32 table rows + fp32 weights, aligned.
 // Header @36 (int32 narrow_wcols): > 0 = a narrowed row carries only its

@@ -363,4 +363,23 @@ hipError_t launch_rank_segments(const float* scores, int64_t n_scores, const int
 hipError_t launch_rank_arena(const void* arena_dev, const float* scores, int64_t scores_len, float* out_vals,
                              int64_t* out_idx, hipStream_t st);
 
+// K7t (topk.hip): the m = min(k[s], n) best scores of each segment - the head
+// of launch_rank_segments' descending order - at entries [0, m) of the
+// segment's span of out_vals / out_idx; entries [m, n) and everything outside
+// the segments are NOT written. k: device int32 [S], per segment; k[s] <= 0
+// skips the segment. Segments longer than topk_select_min() with m at most
+// topk_select_max() are selected (radix select on key << 32 | index) and only
+// the selected ranked; the others run the full network. Otherwise as
+// launch_rank_segments.
+int topk_select_max();
+int topk_select_min();
+hipError_t launch_topk_segments(const float* scores, int64_t n_scores, const int32_t* offsets, const int32_t* k, int S,
+                                int max_len, float* out_vals, int64_t* out_idx, hipStream_t st);
+// The same over the requests of a device request arena: the per-descriptor k
+// comes from the arena's int32 table (header n_topk at 48, payload offset of
+// the table at 56; 0: the request did not ask). The grid returns at once when
+// n_topk is 0; a descriptor that launch_rank_arena would skip writes nothing.
+hipError_t launch_topk_arena(const void* arena_dev, const float* scores, int64_t scores_len, float* out_vals,
+                             int64_t* out_idx, hipStream_t st);
+
 }  // namespace dtfs

@@ -255,6 +255,9 @@ inline LiveConfig live_config_from(const py::dict& d) {
   if (get("narrow_modulo")) c.narrow_modulo = d["narrow_modulo"].cast<int64_t>();
   if (get("narrow_wts_cols")) c.narrow_wts_cols = d["narrow_wts_cols"].cast<int64_t>();
   if (get("rank_outputs")) c.rank_outputs = d["rank_outputs"].cast<bool>();
+  if (get("top_key")) c.top_key = d["top_key"].cast<std::string>();
+  if (get("top_index_key")) c.top_index_key = d["top_index_key"].cast<std::string>();
+  if (get("topk_input_key")) c.topk_input_key = d["topk_input_key"].cast<std::string>();
   return c;
 }
 
@@ -387,6 +390,7 @@ void def_live_methods(py::class_<H>& c) {
             o["narrowed_wts_bf16"] = s.narrowed_wts_bf16;
             o["narrowed_wts_implicit"] = s.narrowed_wts_implicit;
             o["ranked"] = s.ranked;
+            o["topk"] = s.topk;
             o["proposed_steps"] = s.proposed_steps;
             o["joined_steps"] = s.joined_steps;
             o["copy_us"] = s.copy_us;

@@ -59,22 +59,27 @@ void arena_varint_cpu(uint8_t* base) {
 
 ArenaBatch arena_build(uint8_t* base, int64_t capacity, const std::vector<Span>& spans, const std::string& ids_key,
                        const std::string& wts_key, int64_t fields, int64_t max_rows, int64_t varint_chunks,
-                       int64_t n_ranked) {
+                       int64_t n_ranked, const std::vector<int32_t>& topk) {
   std::vector<ArenaItem> items(spans.size());
   for (size_t i = 0; i < spans.size(); ++i) {
     items[i].off = spans[i].first;
     items[i].len = spans[i].second;
   }
-  return arena_build_items(base, capacity, items, ids_key, wts_key, fields, max_rows, varint_chunks, 0, 4, n_ranked);
+  return arena_build_items(base, capacity, items, ids_key, wts_key, fields, max_rows, varint_chunks, 0, 4, n_ranked,
+                           topk);
 }
 
 ArenaBatch arena_build_items(uint8_t* base, int64_t capacity, const std::vector<ArenaItem>& items,
                              const std::string& ids_key, const std::string& wts_key, int64_t fields, int64_t max_rows,
-                             int64_t varint_chunks, int64_t narrow_wcols, int64_t narrow_id_bytes, int64_t n_ranked) {
+                             int64_t varint_chunks, int64_t narrow_wcols, int64_t narrow_id_bytes, int64_t n_ranked,
+                             const std::vector<int32_t>& topk) {
   if (int64_t(items.size()) > kArenaMaxRequests) throw std::invalid_argument("too many requests for one arena");
   if (narrow_wcols < 0 || narrow_wcols > fields) throw std::invalid_argument("narrow_wcols must be in [0, fields]");
   if (narrow_id_bytes != 3 && narrow_id_bytes != 4) throw std::invalid_argument("narrow_id_bytes must be 3 or 4");
   if (n_ranked < 0 || n_ranked > int64_t(items.size())) throw std::invalid_argument("n_ranked must be in [0, requests]");
+  if (!topk.empty() && topk.size() != items.size()) throw std::invalid_argument("topk must hold one k per request");
+  for (const int32_t k : topk)
+    if (k < 0) throw std::invalid_argument("topk entries must not be negative");
   const int64_t idb = narrow_id_bytes;
   const int64_t wcols = narrow_wcols > 0 ? narrow_wcols : fields;  // weights per narrowed row
   uint8_t* payload = base + kArenaPayloadOff;
@@ -117,6 +122,14 @@ ArenaBatch arena_build_items(uint8_t* base, int64_t capacity, const std::vector<
   int64_t n_chunks = 0;
   std::vector<wire::PredictRequestView> views(n);
   int64_t nd = 0, row = 0;
+  // per descriptor: the k of a request that asked for a top-k output, else 0
+  std::vector<int32_t> desc_k;
+  int64_t n_topk = 0;
+  auto note_k = [&](size_t i) {
+    if (topk.empty()) return;
+    desc_k.push_back(topk[i]);
+    if (topk[i] > 0) ++n_topk;
+  };
   // framing parse, one request per pool task (packed varint fields are
   // counted here: ~6 bytes per id for ids over 2^40)
   // Packed varint ids are counted once, per GPU decode chunk (the counts
@@ -171,6 +184,7 @@ ArenaBatch arena_build_items(uint8_t* base, int64_t capacity, const std::vector<
       desc[4 * nd + 1] = items[i].wts_off | (int64_t(items[i].wkind) << kWtsKindShift);
       desc[4 * nd + 2] = rows;
       desc[4 * nd + 3] = row;
+      note_k(i);
       ++nd;
       out.rows[i] = rows;
       out.offsets[i] = row;
@@ -242,6 +256,7 @@ ArenaBatch arena_build_items(uint8_t* base, int64_t capacity, const std::vector<
     desc[4 * nd + 1] = wts_raw ? j.wts_off : j.wts_scratch;
     desc[4 * nd + 2] = rows;
     desc[4 * nd + 3] = row;
+    note_k(i);
     ++nd;
     out.rows[i] = rows;
     out.offsets[i] = row;
@@ -274,20 +289,23 @@ ArenaBatch arena_build_items(uint8_t* base, int64_t capacity, const std::vector<
     if (!errs[k].empty()) out.errors[jobs[k].req] = errs[k];
   }
   // per-row offset table: {ids_off, wts_off} int32 (payload-relative), then
-  // the varint chunk table (both copied to the GPU), then the device-only
-  // region the varint kernel decodes ids into
+  // the varint chunk table, then - only when a request of the batch asked for
+  // a top-k output - the per-descriptor int32 k table (all copied to the GPU),
+  // then the device-only region the varint kernel decodes ids into
   const int64_t rt = (std::max(end, scratch) + 63) & ~int64_t(63);
   const int64_t vt = (rt + row * 8 + 63) & ~int64_t(63);
   const int64_t vt_end = vt + n_chunks * int64_t(sizeof(VarintChunk));
-  int64_t dec = (vt_end + 63) & ~int64_t(63);
+  const int64_t kt = n_topk > 0 ? (vt_end + 63) & ~int64_t(63) : 0;
+  const int64_t copied_end = n_topk > 0 ? kt + 4 * nd : vt_end;
+  int64_t dec = (copied_end + 63) & ~int64_t(63);
   for (const GpuJob& g : gjobs) dec += g.ne * 8;
-  if (std::max(vt_end, dec) > cap) throw std::invalid_argument("arena too small for the row table");
-  if (std::max(vt_end, dec) > int64_t(INT32_MAX)) throw std::invalid_argument("arena payload exceeds 2 GiB");
+  if (std::max(copied_end, dec) > cap) throw std::invalid_argument("arena too small for the row table");
+  if (std::max(copied_end, dec) > int64_t(INT32_MAX)) throw std::invalid_argument("arena payload exceeds 2 GiB");
   {
     // chunk tables, one request per pool task
     VarintChunk* vtab = reinterpret_cast<VarintChunk*>(payload + vt);
     std::vector<int64_t> first_chunk(gjobs.size()), dst(gjobs.size());
-    int64_t d = (vt_end + 63) & ~int64_t(63), c = 0;
+    int64_t d = (copied_end + 63) & ~int64_t(63), c = 0;
     for (size_t k = 0; k < gjobs.size(); ++k) {
       desc[4 * gjobs[k].desc + 0] = d;
       dst[k] = d;
@@ -337,10 +355,13 @@ ArenaBatch arena_build_items(uint8_t* base, int64_t capacity, const std::vector<
   *reinterpret_cast<int32_t*>(base + 36) = int32_t(narrow_wcols);
   *reinterpret_cast<int32_t*>(base + 40) = int32_t(idb);
   *reinterpret_cast<int32_t*>(base + 44) = int32_t(n_ranked);
+  *reinterpret_cast<int32_t*>(base + 48) = int32_t(n_topk);
+  *reinterpret_cast<int64_t*>(base + 56) = kt;
+  if (n_topk > 0) std::memcpy(payload + kt, desc_k.data(), size_t(4 * nd));
   out.total_rows = row;
   out.n_valid = nd;
   out.n_gpu_varint = int64_t(gjobs.size());
-  out.used_bytes = kArenaPayloadOff + vt_end;
+  out.used_bytes = kArenaPayloadOff + copied_end;
   return out;
 }
 

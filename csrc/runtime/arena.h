@@ -7,6 +7,11 @@
 //   [40]  int32 narrow_id_bytes (3: narrowed rows are packed 3-byte rows; else 4)
 //   [44]  int32 n_ranked   (requests of the batch that asked for a ranked output;
 //                           0: the step's rank kernel, csrc/kernels/rank.hip, returns at once)
+//   [48]  int32 n_topk     (requests of the batch that asked for a top-k output;
+//                           0: the step's top-k kernels, csrc/kernels/topk.hip, return at once)
+//   [56]  int64 topk_table_off (payload offset of n_req int32: each descriptor's k,
+//                           0 = that request did not ask; behind the varint chunk
+//                           table, present - and counted in used_bytes - only when n_topk > 0)
 //   [64]  n_req x {ids_off, wts_off, rows, dst_row} int64 (offsets into payload)
 //   [kArenaPayloadOff] payload: serialized PredictRequests (+ scratch for
 //                      host-decoded typed fields), then at row_table_off a
@@ -83,9 +88,12 @@ std::vector<Span> arena_place(uint8_t* arena, int64_t capacity, const std::vecto
 // varint_chunks: capacity of the GPU varint chunk table (0: packed int64_val
 // ids are decoded on the host pool instead).
 // n_ranked: the header's count of requests that asked for a ranked output.
+// topk: empty, or per request the k of the top-k output it asked for (0: it
+// did not). An arena built with no k > 0 is byte for byte the arena built
+// without the argument.
 ArenaBatch arena_build(uint8_t* arena, int64_t capacity, const std::vector<Span>& spans, const std::string& ids_key,
                        const std::string& wts_key, int64_t fields, int64_t max_rows, int64_t varint_chunks = 0,
-                       int64_t n_ranked = 0);
+                       int64_t n_ranked = 0, const std::vector<int32_t>& topk = {});
 // Same over a mix of serialized and narrowed requests (results in item order).
 // narrow_id_bytes 3: narrowed ids are 3-byte rows (stride 3 F, header @40).
 // narrow_wcols > 0: narrowed requests carry only their rows' first
@@ -94,7 +102,7 @@ ArenaBatch arena_build(uint8_t* arena, int64_t capacity, const std::vector<Span>
 ArenaBatch arena_build_items(uint8_t* arena, int64_t capacity, const std::vector<ArenaItem>& items,
                              const std::string& ids_key, const std::string& wts_key, int64_t fields, int64_t max_rows,
                              int64_t varint_chunks = 0, int64_t narrow_wcols = 0, int64_t narrow_id_bytes = 4,
-                             int64_t n_ranked = 0);
+                             int64_t n_ranked = 0, const std::vector<int32_t>& topk = {});
 
 // Host reference of the GPU varint kernel: fills the arena's device-only id
 // region from its chunk table (a no-op when the build decoded on the host).

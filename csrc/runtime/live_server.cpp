@@ -64,6 +64,8 @@ LiveServer::LiveServer(StepBackend* backend, LiveConfig cfg, std::vector<std::pa
   for (int b = 0; ranks_ && b < int(bk.size()); ++b)
     for (int s = 0; ranks_ && s < S; ++s)
       ranks_ = backend_->ranked_scores(s, b) != nullptr && backend_->ranked_index(s, b) != nullptr;
+  // the per-request k table arena_build appends when a request asks for a top-k output
+  if (ranks_) arena_budget_ -= 4 * kArenaMaxRequests + 64;
   paused_ = cfg_.start_paused;
   launcher_ = std::thread([this] { launcher_loop(); });
   completer_ = std::thread([this] { completer_loop(); });
@@ -75,6 +77,38 @@ LiveServer::~LiveServer() {
     close();
   } catch (...) {
   }
+}
+
+const std::string& LiveServer::key_of(uint8_t w) const {
+  switch (w) {
+    case kWantSorted: return cfg_.sorted_key;
+    case kWantIndex: return cfg_.index_key;
+    case kWantTop: return cfg_.top_key;
+    case kWantTopIndex: return cfg_.top_index_key;
+    default: return cfg_.output_key;
+  }
+}
+
+// The request's k: one DT_INT32 / DT_INT64 value >= 1 of shape [] or [1], in
+// tensor_content or the typed field (serving/service.py _top_k reads the same).
+bool LiveServer::parse_top_k(const wire::TensorView& in, int64_t* k, std::string* why) {
+  if (in.dtype != wire::DT_INT32 && in.dtype != wire::DT_INT64) return *why = "must be DT_INT32 or DT_INT64", false;
+  if (in.unknown_rank || in.shape.size() > 1 || (in.shape.size() == 1 && in.shape[0] != 1))
+    return *why = "must have shape [] or [1], got " + shape_str(in.shape), false;
+  wire::TensorView t = in;
+  if (t.num_values < 0) {  // packed varints the framing parse left uncounted
+    t.num_values = int64_t(t.unpacked.size());
+    for (const wire::Span& sp : t.packed) t.num_values += wire::count_varint_terminators(sp.p, sp.n);
+  }
+  if (t.content.n == 0 && t.num_values != 1) return *why = "must hold exactly one value", false;
+  int64_t v = 0;
+  wire::DecodeOpts o;
+  o.dst = wire::DstType::I64;
+  std::string err;
+  if (!wire::decode_into(t, &v, 1, o, &err)) return *why = "is malformed: " + err, false;
+  if (v < 1) return *why = "must be at least 1, got " + std::to_string(v), false;
+  *k = v;
+  return true;
 }
 
 int64_t LiveServer::need_of(int64_t len, int64_t rows) const {
@@ -132,11 +166,27 @@ bool LiveServer::admit(const uint8_t* data, size_t n, int64_t deadline_us, Compl
         want |= k == cfg_.sorted_key ? kWantSorted : kWantIndex;
         continue;
       }
+      if (ranks_ && (k == cfg_.top_key || k == cfg_.top_index_key)) {
+        want |= k == cfg_.top_key ? kWantTop : kWantTopIndex;
+        continue;
+      }
       return reject(kCallerPath, "output " + k + " is produced by the general path");
     }
     return reject(kInvalidArgument, "output tensor alias not found in signature: " + k);
   }
   const bool ranked = (want & (kWantSorted | kWantIndex)) != 0;
+  const bool tops = (want & (kWantTop | kWantTopIndex)) != 0;
+  // the slot's one pair of ranked buffers holds a request's full rank or its
+  // top k, not both
+  if (ranked && tops)
+    return reject(kCallerPath, "sorted and top-k outputs in one request are produced by the general path");
+  int64_t top_k = 0;
+  if (tops) {
+    const wire::TensorView* tk = v.find(cfg_.topk_input_key);
+    std::string why;
+    if (!tk) return reject(kInvalidArgument, "top-k outputs need the input " + cfg_.topk_input_key);
+    if (!parse_top_k(*tk, &top_k, &why)) return reject(kInvalidArgument, cfg_.topk_input_key + " " + why);
+  }
   const wire::TensorView* ti = v.find(cfg_.ids_key);
   const wire::TensorView* tw = v.find(cfg_.wts_key);
   if (!ti || !tw)
@@ -153,11 +203,11 @@ bool LiveServer::admit(const uint8_t* data, size_t n, int64_t deadline_us, Compl
                           cfg_.version >= 0, cfg_.version};
   if (rows == 0) {
     std::vector<wire::TensorOut> outs;
-    for (const uint8_t w : {kWantScores, kWantSorted, kWantIndex}) {
+    for (const uint8_t w : {kWantScores, kWantSorted, kWantIndex, kWantTop, kWantTopIndex}) {
       if (!(want & w)) continue;
       wire::TensorOut t;
-      t.key = w == kWantScores ? cfg_.output_key : (w == kWantSorted ? cfg_.sorted_key : cfg_.index_key);
-      t.dtype = w == kWantIndex ? wire::DT_INT64 : wire::DT_FLOAT;
+      t.key = key_of(w);
+      t.dtype = (w == kWantIndex || w == kWantTopIndex) ? wire::DT_INT64 : wire::DT_FLOAT;
       t.shape = {0};
       outs.push_back(std::move(t));
     }
@@ -165,7 +215,7 @@ bool LiveServer::admit(const uint8_t* data, size_t n, int64_t deadline_us, Compl
     return true;
   }
   // one workgroup ranks one request: longer ones keep the general path
-  if (ranked && rows > kMaxRankedRows)
+  if ((ranked || tops) && rows > kMaxRankedRows)
     return reject(kCallerPath, "ranked outputs of more than " + std::to_string(kMaxRankedRows) +
                                    " rows are produced by the general path");
   if (rows > max_rows_)
@@ -254,6 +304,7 @@ bool LiveServer::admit(const uint8_t* data, size_t n, int64_t deadline_us, Compl
     Arena& o = arenas_[size_t(a)];
     Pending p{0, int64_t(n), rows, deadline_us, t0, std::move(done)};
     p.want = want;
+    p.top_k = int32_t(std::min<int64_t>(top_k, kMaxRankedRows));
     if (narrow) {
       p.narrow = true;
       p.ids_off = align64(o.used);
@@ -541,9 +592,14 @@ void LiveServer::launcher_loop() {
     if (!expired.empty()) fail_all(expired, kDeadlineExceeded, "request deadline exceeded while queued");
     std::vector<ArenaItem> items(live.size());
     int64_t n_ranked = 0;  // arena header: 0 lets the step's rank kernel return at once
+    std::vector<int32_t> topk;  // per request k, only when a request of the batch asked for a top-k output
     for (size_t i = 0; i < live.size(); ++i) {
       const Pending& p = live[i];
       if (p.want & (kWantSorted | kWantIndex)) ++n_ranked;
+      if (p.want & (kWantTop | kWantTopIndex)) {
+        if (topk.empty()) topk.assign(live.size(), 0);
+        topk[i] = p.top_k;
+      }
       ArenaItem& it = items[i];
       it.off = p.off;
       it.len = p.len;
@@ -558,7 +614,7 @@ void LiveServer::launcher_loop() {
     try {
       trace::Range tr("live_build");
       batch = arena_build_items(ar.base, ar.capacity, items, cfg_.ids_key, cfg_.wts_key, cfg_.fields, max_rows_,
-                                cfg_.varint_chunks, cfg_.narrow_wts_cols, narrow_id_bytes(), n_ranked);
+                                cfg_.varint_chunks, cfg_.narrow_wts_cols, narrow_id_bytes(), n_ranked, topk);
     } catch (const std::exception& e) {
       fail_all(live, kInternal, std::string("batch build failed: ") + e.what());
       if (agree_) {  // the other ranks launch step k: this rank cannot skip it
@@ -703,7 +759,7 @@ void LiveServer::completer_loop() {
     const int64_t sc_len = backend_->scores_len(f.slot, f.bucket);
     const float* rk_val = backend_->ranked_scores(f.slot, f.bucket);
     const int64_t* rk_idx = backend_->ranked_index(f.slot, f.bucket);
-    int64_t n_ok = 0, n_bad = 0, n_ranked = 0;
+    int64_t n_ok = 0, n_bad = 0, n_ranked = 0, n_topk = 0;
     std::vector<wire::TensorOut> outs;
     {
       trace::Range tr("live_encode");
@@ -719,25 +775,27 @@ void LiveServer::completer_loop() {
           r.code = kInternal;
           r.message = "scores buffer smaller than the batch";
           ++n_bad;
-        } else if ((p.want & (kWantSorted | kWantIndex)) && (!rk_val || !rk_idx)) {
+        } else if ((p.want & (kWantSorted | kWantIndex | kWantTop | kWantTopIndex)) && (!rk_val || !rk_idx)) {
           r.code = kInternal;
           r.message = "the step produced no ranked outputs";
           ++n_bad;
         } else {
-          // prediction_node, sorted_prediction, sorted_index: the order of the
-          // general path (serving/service.py _outputs)
+          // prediction_node, sorted_prediction, sorted_index, top_prediction,
+          // top_index: the order of the general path (serving/service.py
+          // _outputs). The top-k kernel wrote only the first min(k, rows)
+          // entries of the request's span of the ranked buffers.
           outs.clear();
-          for (const uint8_t w : {kWantScores, kWantSorted, kWantIndex}) {
+          for (const uint8_t w : {kWantScores, kWantSorted, kWantIndex, kWantTop, kWantTopIndex}) {
             if (!(p.want & w)) continue;
+            const bool top = w == kWantTop || w == kWantTopIndex;
             wire::TensorOut t;
-            t.shape = {f.batch.rows[i]};
-            t.n = f.batch.rows[i];
-            if (w == kWantIndex) {
-              t.key = cfg_.index_key;
+            t.n = top ? std::min<int64_t>(p.top_k, f.batch.rows[i]) : f.batch.rows[i];
+            t.shape = {t.n};
+            t.key = key_of(w);
+            if (w == kWantIndex || w == kWantTopIndex) {
               t.dtype = wire::DT_INT64;
               t.data = rk_idx + f.batch.offsets[i];
             } else {
-              t.key = w == kWantScores ? cfg_.output_key : cfg_.sorted_key;
               t.dtype = wire::DT_FLOAT;
               t.data = (w == kWantScores ? sc : rk_val) + f.batch.offsets[i];
             }
@@ -745,6 +803,7 @@ void LiveServer::completer_loop() {
           }
           r.response = wire::encode_predict_response(spec, outs);
           if (p.want & (kWantSorted | kWantIndex)) ++n_ranked;
+          if (p.want & (kWantTop | kWantTopIndex)) ++n_topk;
           ++n_ok;
         }
         r.t_arrive = p.t_arrive;
@@ -761,6 +820,7 @@ void LiveServer::completer_loop() {
       pending_ -= int64_t(f.pend.size());
       st_.completed += n_ok;
       st_.ranked += n_ranked;
+      st_.topk += n_topk;
       st_.failed += n_bad;
       st_.wait_us += double(t1 - t0);
       st_.encode_us += double(t2 - t1);

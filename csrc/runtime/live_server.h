@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "arena.h"
+#include "wire/tensor_codec.h"
 #include "step_control.h"
 
 namespace dtfs {
@@ -143,6 +144,12 @@ struct LiveConfig {
   // instead of getting kCallerPath, up to kMaxRankedRows rows each.
   bool rank_outputs = false;
   std::string sorted_key = "sorted_prediction", index_key = "sorted_index";
+  // Top-k outputs (csrc/kernels/topk.hip behind the rank kernel in the same
+  // step, writing the same two buffers): a request naming top_key /
+  // top_index_key carries its k in the input topk_input_key. Served here under
+  // the same conditions; one that also names sorted_key / index_key gets
+  // kCallerPath (a slot has one pair of ranked buffers).
+  std::string top_key = "top_prediction", top_index_key = "top_index", topk_input_key = "top_k";
 };
 constexpr int64_t kMaxRankedRows = 16384;  // csrc/kernels/rank.hip: one workgroup's segment
 
@@ -152,7 +159,8 @@ struct LiveStats {
   int64_t full_steps = 0, timeout_steps = 0, eager_steps = 0, blocked_submits = 0, narrowed = 0;
   // narrowed requests whose weights travelled as bf16 (all exact) / not at all (all 1.0)
   int64_t narrowed_wts_bf16 = 0, narrowed_wts_implicit = 0;
-  int64_t ranked = 0;  // completed requests that got a ranked output from the step
+  int64_t ranked = 0;  // completed requests that got a ranked (sorted_*) output from the step
+  int64_t topk = 0;    // completed requests that got a top-k output from the step
   // cluster mode: steps this rank proposed / joined with a batch of its own /
   // joined with nothing queued (empty_steps counts those too)
   int64_t proposed_steps = 0, joined_steps = 0;
@@ -207,8 +215,9 @@ class LiveServer {
     int wkind = 0;                     // narrow: WtsKind of the weights (runtime/narrow.h)
     // outputs the request's filter names (kWant*); an empty filter: kWantScores
     uint8_t want = 1;
+    int32_t top_k = 0;  // kWantTop / kWantTopIndex: the request's k (>= 1), capped at kMaxRankedRows
   };
-  enum : uint8_t { kWantScores = 1, kWantSorted = 2, kWantIndex = 4 };
+  enum : uint8_t { kWantScores = 1, kWantSorted = 2, kWantIndex = 4, kWantTop = 8, kWantTopIndex = 16 };
   struct Arena {
     uint8_t* base = nullptr;
     int64_t capacity = 0;
@@ -228,6 +237,8 @@ class LiveServer {
   void watcher_loop();  // cluster mode: heartbeats, peer liveness, wakes an idle launcher
   int bucket_for(int64_t rows) const;
   int64_t need_of(int64_t len, int64_t rows) const;
+  const std::string& key_of(uint8_t want_bit) const;
+  static bool parse_top_k(const wire::TensorView& t, int64_t* k, std::string* why);
   void fail_all(std::vector<Pending>& ps, int code, const std::string& msg);
   void go_broken(const std::string& why);  // call WITHOUT mu_ held
   void release(int arena, int slot);

@@ -50,6 +50,10 @@ class FanoutResult:
     sorted_scores: Optional[torch.Tensor] = None
     order: Optional[torch.Tensor] = None       # candidate index of each sorted score
     shard_order: Optional[List[int]] = None    # order shards were concatenated in
+    # FanoutClient(top_k=N): the N best scores of all candidates, descending (ties by candidate index, NaN
+    # last), and their candidate indices; ``scores`` is then empty (the shards return only their top lists)
+    top_scores: Optional[torch.Tensor] = None
+    top_index: Optional[torch.Tensor] = None
 
 
 class ShardError(RuntimeError):
@@ -58,16 +62,40 @@ class ShardError(RuntimeError):
         self.shard, self.backend, self.cause = shard, backend, cause
 
 
+def top_order(vals: np.ndarray, index: np.ndarray) -> np.ndarray:
+    """Permutation that puts (score, candidate index) pairs into the serving
+    order of top-k outputs: descending score, NaN last, -0.0 and +0.0 tied,
+    ties by ascending candidate index (csrc/kernels/sort.hip's key)."""
+    v = np.ascontiguousarray(vals, dtype=np.float32)
+    u = v.view(np.uint32).copy()
+    u[v == 0] = 0
+    key = ~np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000)).astype(np.uint32)
+    key[np.isnan(v)] = np.uint32(0xFFFFFFFE)
+    return np.lexsort((np.asarray(index, dtype=np.int64), key))
+
+
 class FanoutClient:
     def __init__(self, backends: Sequence[Backend], spec: RequestSpec = RequestSpec(), pool_threads: int = 16,
                  full_async: bool = True, sort_scores: bool = True, timeout_s: Optional[float] = None,
-                 executor: Optional[cf.Executor] = None, failover: bool = False, cooldown_s: float = 5.0):
-        """``failover``: a shard whose backend fails (error or ``timeout_s``)
+                 executor: Optional[cf.Executor] = None, failover: bool = False, cooldown_s: float = 5.0,
+                 top_k: Optional[int] = None):
+        """``top_k=N``: every shard is asked for ``top_prediction`` /
+        ``top_index`` (its own N best) only, and the per-shard lists are merged
+        into the global top N (``FanoutResult.top_scores`` / ``top_index``,
+        candidate index = the shard's row offset + its local index). Shards are
+        cut on row boundaries in order, so the merge order - descending score,
+        ties by global candidate index - is the order one server would give for
+        all candidates. ``None``: scores of every candidate, as before.
+
+        ``failover``: a shard whose backend fails (error or ``timeout_s``)
         is re-split over the backends still healthy and retried, and the failed
         backend is skipped by new requests for ``cooldown_s`` (degraded mode;
         the reference abandons the request, DCNClient.java:185-188)."""
         if not backends:
             raise ValueError("need at least one backend")
+        if top_k is not None and int(top_k) < 1:
+            raise ValueError("top_k must be at least 1")
+        self.top_k = None if top_k is None else int(top_k)
         self.backends = list(backends)
         self.spec = spec
         self.full_async = full_async
@@ -97,8 +125,13 @@ class FanoutClient:
     # -- encoding -------------------------------------------------------------
     def encode(self, ids: torch.Tensor, wts: torch.Tensor) -> bytes:
         s = self.spec
+        if self.top_k is None:
+            return self.nat.encode_predict_request(s.model_name, s.signature_name, s.version,
+                                                   [(s.ids_key, ids), (s.wts_key, wts)], s.raw)
         return self.nat.encode_predict_request(s.model_name, s.signature_name, s.version,
-                                               [(s.ids_key, ids), (s.wts_key, wts)], s.raw)
+                                               [(s.ids_key, ids), (s.wts_key, wts),
+                                                ("top_k", torch.tensor([self.top_k], dtype=torch.int64))], s.raw,
+                                               ["top_prediction", "top_index"])
 
     def decode_scores(self, data: bytes) -> torch.Tensor:
         r = pb.PredictResponse.FromString(data)
@@ -107,17 +140,37 @@ class FanoutClient:
             return torch.from_numpy(np.frombuffer(t.tensor_content, dtype="<f4").copy())
         return torch.tensor(list(t.float_val), dtype=torch.float32)
 
+    @staticmethod
+    def _tensor(t, dtype) -> torch.Tensor:
+        if t.tensor_content:
+            return torch.from_numpy(np.frombuffer(t.tensor_content, dtype="<f4" if dtype == torch.float32 else "<i8").copy())
+        return torch.tensor(list(t.float_val if dtype == torch.float32 else t.int64_val), dtype=dtype)
+
+    def decode_top(self, data: bytes, row0: int = 0):
+        """(scores fp32 [m], candidate indices int64 [m] + row0) of a shard's top-k response."""
+        r = pb.PredictResponse.FromString(data)
+        if "top_prediction" not in r.outputs or "top_index" not in r.outputs:
+            raise ValueError("response carries no top_prediction / top_index")
+        vals = self._tensor(r.outputs["top_prediction"], torch.float32)
+        idx = self._tensor(r.outputs["top_index"], torch.int64)
+        if vals.numel() != idx.numel():
+            raise ValueError("top_prediction and top_index differ in length")
+        return vals, idx + row0
+
     # -- fan-out ----------------------------------------------------------------
-    def _call(self, i: int, ids: torch.Tensor, wts: torch.Tensor) -> torch.Tensor:
+    def _call(self, i: int, ids: torch.Tensor, wts: torch.Tensor, row0: int = 0):
+        """Scores of the rows; with ``top_k`` their (top scores, top indices +
+        row0) instead."""
         be = self.backends[i]
         try:
-            return self.decode_scores(be.predict(self.encode(ids, wts), self.timeout_s))
+            data = be.predict(self.encode(ids, wts), self.timeout_s)
+            return self.decode_scores(data) if self.top_k is None else self.decode_top(data, row0)
         except BaseException as e:  # noqa: BLE001
             raise ShardError(i, be.name, e) from e
 
-    def _shard_call(self, i: int, ids: torch.Tensor, wts: torch.Tensor) -> torch.Tensor:
+    def _shard_call(self, i: int, ids: torch.Tensor, wts: torch.Tensor, row0: int = 0):
         try:
-            return self._call(i, ids, wts)
+            return self._call(i, ids, wts, row0)
         except ShardError:
             if not self.failover:
                 raise
@@ -131,10 +184,12 @@ class FanoutClient:
             for j, (s, k) in zip(alive, split_rows(ids.shape[0], len(alive))):
                 if k:
                     try:
-                        outs.append(self._call(j, ids[s:s + k], wts[s:s + k]))
+                        outs.append(self._call(j, ids[s:s + k], wts[s:s + k], row0 + s))
                     except ShardError:
                         self.mark_down(j)
                         raise
+            if self.top_k is not None:  # the sub-shards' lists: merged with the others'
+                return torch.cat([v for v, _ in outs]), torch.cat([x for _, x in outs])
             return torch.cat(outs)
 
     def predict_async(self, ids, wts) -> cf.Future:
@@ -144,10 +199,13 @@ class FanoutClient:
         n = ids.shape[0]
         targets = self.healthy() if self.failover else list(range(len(self.backends)))
         parts = [(targets[i], s, k) for i, (s, k) in enumerate(split_rows(n, len(targets))) if k > 0]
-        futs = {self.pool.submit(self._shard_call, i, ids[s:s + k], wts[s:s + k]): i for i, s, k in parts}
+        futs = {self.pool.submit(self._shard_call, i, ids[s:s + k], wts[s:s + k], s): i for i, s, k in parts}
         out: cf.Future = cf.Future()
         if not futs:
-            out.set_result(FanoutResult(scores=torch.empty(0)))
+            res = FanoutResult(scores=torch.empty(0))
+            if self.top_k is not None:
+                res.top_scores, res.top_index = torch.empty(0), torch.empty(0, dtype=torch.int64)
+            out.set_result(res)
             return out
         state = {"left": len(futs), "done": []}
         lock = threading.Lock()
@@ -164,6 +222,14 @@ class FanoutClient:
                 else:  # mode B: completion order
                     order = list(state["done"])
                 by_idx = {futs[g]: g for g in futs}
+                if self.top_k is not None:
+                    lists = [by_idx[i].result() for i in order]
+                    vals = torch.cat([v for v, _ in lists])
+                    gidx = torch.cat([x for _, x in lists])
+                    keep = torch.from_numpy(top_order(vals.numpy(), gidx.numpy())[:self.top_k].copy())
+                    out.set_result(FanoutResult(scores=torch.empty(0), shard_order=order, top_scores=vals[keep],
+                                                top_index=gidx[keep]))
+                    return
                 scores = torch.cat([by_idx[i].result() for i in order])
                 res = FanoutResult(scores=scores, shard_order=order)
                 if self.sort_scores:

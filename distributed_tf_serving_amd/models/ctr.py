@@ -55,10 +55,13 @@ class CTRModel(nn.Module):
     def signature(self) -> Dict[str, Dict]:
         F = self.cfg.num_fields
         return {
-            "inputs": {"feat_ids": ("DT_INT64", [-1, F]), "feat_wts": ("DT_FLOAT", [-1, F])},
-            # ranked outputs: produced when named in output_filter (serving/service.py)
+            # top_k: optional, one value >= 1 (DT_INT32 also accepted), read only when a top_* output is named
+            "inputs": {"feat_ids": ("DT_INT64", [-1, F]), "feat_wts": ("DT_FLOAT", [-1, F]),
+                       "top_k": ("DT_INT64", [])},
+            # ranked / top-k outputs: produced when named in output_filter (serving/service.py)
             "outputs": {"prediction_node": ("DT_FLOAT", [-1]), "sorted_prediction": ("DT_FLOAT", [-1]),
-                        "sorted_index": ("DT_INT64", [-1])},
+                        "sorted_index": ("DT_INT64", [-1]), "top_prediction": ("DT_FLOAT", [-1]),
+                        "top_index": ("DT_INT64", [-1])},
             "method_name": "tensorflow/serving/predict",
         }
 

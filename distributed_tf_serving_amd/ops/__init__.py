@@ -1027,3 +1027,104 @@ def rank_arena(arena: torch.Tensor, scores: torch.Tensor, out_vals: torch.Tensor
         if rows <= 0 or rows > RANK_MAX or r0 < 0 or r0 + rows > n:
             continue
         _rank_into(scores, r0, r0 + rows, False, -1, out_vals, out_idx)
+
+
+# ------------------------------------------------------------------ K7t
+def _is_pinned_host(t: torch.Tensor) -> bool:
+    return (not t.is_cuda) and t.is_pinned()
+
+
+def topk_segments(scores: torch.Tensor, offsets, k, out=None):
+    """The ``min(k[s], n)`` best scores of each of S segments of one fp32 score
+    buffer, one launch: segment s is ``scores[offsets[s]:offsets[s + 1]]`` and
+    ``k`` holds one int per segment (0 skips it). Returns (values [N] fp32,
+    index [N] int64) in the buffer's own layout: the head of
+    ``rank_segments(descending=True)`` - descending scores, ties by candidate
+    index, NaN last, and their segment-local candidate indices - at the first
+    ``min(k[s], n)`` positions of the segment. NOTHING else is written: with
+    ``out=(values, index)`` positions past that and outside every segment keep
+    what they held (0 / -1 in fresh outputs). GPU (``scores`` / ``out`` on the
+    device or in pinned host memory): one workgroup per segment of at most
+    RANK_MAX scores; long segments with a small k are selected (radix select)
+    and only the selected ranked (csrc/kernels/topk.hip)."""
+    if scores.dim() != 1:
+        raise ValueError("scores must be a 1-D tensor")
+    N = scores.numel()
+    off = torch.as_tensor(offsets).detach().to("cpu", torch.int64).reshape(-1)
+    if off.numel() < 1:
+        raise ValueError("offsets must hold at least one entry")
+    kt = torch.as_tensor(k)
+    if kt.is_floating_point() or kt.dtype == torch.bool:
+        raise ValueError("k must hold integers")
+    kt = kt.detach().to("cpu", torch.int64).reshape(-1)
+    lens = off[1:] - off[:-1]
+    if kt.numel() != lens.numel():
+        raise ValueError(f"k must hold one entry per segment ({lens.numel()}), got {kt.numel()}")
+    if bool((kt < 0).any()):
+        raise ValueError("k must not be negative")
+    if int(off[0]) < 0 or bool((lens < 0).any()):
+        raise ValueError("offsets must be ascending and not negative")
+    if int(off[-1]) > N:
+        raise ValueError(f"offsets run past the {N} scores")
+    if out is not None:
+        ov, oi = out
+        if ov.dim() != 1 or oi.dim() != 1 or ov.numel() != N or oi.numel() != N:
+            raise ValueError(f"out must be (values [N], index [N]) as long as the {N} scores")
+        if ov.dtype != torch.float32 or oi.dtype != torch.int64:
+            raise ValueError("out must be (fp32 values, int64 index)")
+    gpu = scores.is_cuda or (out is not None and (out[0].is_cuda or out[1].is_cuda)) or \
+        (_is_pinned_host(scores) and out is not None and _is_pinned_host(out[0]) and _is_pinned_host(out[1])
+         and torch.cuda.is_available())
+    if gpu:
+        if lens.numel() and int(lens.max()) > RANK_MAX:
+            raise ValueError(f"a segment has {int(lens.max())} scores; the kernel takes at most {RANK_MAX}")
+        sf = scores if scores.dtype == torch.float32 and scores.is_contiguous() else scores.contiguous().float()
+        if out is None:
+            out = (torch.zeros(N, dtype=torch.float32, device=sf.device),
+                   torch.full((N,), -1, dtype=torch.int64, device=sf.device))
+        hip().topk_segments(sf, off, kt, out[0], out[1])
+        return out
+    sf = scores.float()
+    vals, idx = (torch.zeros(N), torch.full((N,), -1, dtype=torch.int64)) if out is None else out
+    for a, b, kk in zip(off[:-1].tolist(), off[1:].tolist(), kt.tolist()):
+        if b > a and kk > 0:
+            _topk_into(sf, a, b, kk, vals, idx)
+    return vals, idx
+
+
+def _topk_into(sf, a, b, k, vals, idx) -> None:
+    s, p = sort_scores(sf[a:b], True, min(int(k), b - a))
+    vals[a:a + s.numel()] = s
+    idx[a:a + s.numel()] = p
+
+
+def topk_arena(arena: torch.Tensor, scores: torch.Tensor, out_vals: torch.Tensor, out_idx: torch.Tensor) -> None:
+    """:func:`topk_segments` over the requests of a built request arena
+    (serving/arena.py): request d's ``min(k, rows)`` best scores of
+    ``scores[dst_row:dst_row + rows]`` go to the first positions of that span of
+    ``out_vals`` / ``out_idx`` (int64 request-local candidate indices), with
+    the request's k from the arena's k table (0: it did not ask). Nothing is
+    written when the header's ``n_topk`` is 0, nor for a request that
+    :func:`rank_arena` would skip. Runs behind ``rank_arena`` on the same
+    buffers in a served step: a top-k request's head overwrites what the rank
+    kernel left there. GPU: capturable like ``rank_arena``. CPU: the same
+    header, descriptors and table read from the host arena."""
+    if arena.is_cuda:
+        hip().topk_arena(arena, scores, out_vals, out_idx)
+        return
+    hdr = arena[:64].contiguous().view(torch.int32)
+    n_req, n_topk = int(hdr[0]), int(hdr[12])
+    if n_topk <= 0:
+        return
+    tab = int(arena[56:64].contiguous().view(torch.int64)[0])
+    if tab < 0 or tab % 4:
+        return
+    n_req = min(n_req, native().ARENA_MAX_REQUESTS)
+    desc = arena[64:64 + 32 * n_req].contiguous().view(torch.int64).reshape(n_req, 4)
+    t0 = native().ARENA_PAYLOAD_OFF + tab
+    ks = arena[t0:t0 + 4 * n_req].contiguous().view(torch.int32).tolist()
+    n = scores.numel()
+    for (rows, r0), kk in zip(desc[:, 2:].tolist(), ks):
+        if kk <= 0 or rows <= 0 or rows > RANK_MAX or r0 < 0 or r0 + rows > n:
+            continue
+        _topk_into(scores, r0, r0 + rows, kk, out_vals, out_idx)

@@ -140,8 +140,10 @@ class FanoutEngine:
         the fan-out mode on a 1-rank job (exercises that path on one GPU).
 
         ``rank_on_gpu`` (arena ingest): a local step also ranks every
-        request's scores (``ops.rank_arena`` after the forward, in the step's
-        graph) into :meth:`host_rank`, for the live server's ranked outputs."""
+        request's scores (``ops.rank_arena``, then ``ops.topk_arena`` for the
+        requests that asked for their top k, after the forward, in the step's
+        graph) into :meth:`host_rank`, for the live server's ranked and top-k
+        outputs."""
         if mode not in MODES:
             raise ValueError(f"mode must be one of {MODES}")
         if ingest not in ("packed", "arena"):
@@ -685,6 +687,9 @@ class FanoutEngine:
                 from .. import ops
 
                 ops.rank_arena(arena_dev, out, rank[0], rank[1])
+                # then the head of every request that asked for its top k, over
+                # what the rank kernel left there (also an early-out grid)
+                ops.topk_arena(arena_dev, out, rank[0], rank[1])
 
         side = torch.cuda.Stream(self.dev)
         side.wait_stream(cur)

@@ -11,7 +11,10 @@ uniform.
 
 Layout (shared with csrc): header (n_req int32 @0, total_rows int64 @8,
 row_table_off int64 @16, n_ranked int32 @44: how many requests of the batch
-asked for a ranked output - 0 lets the step's rank kernel return at once),
+asked for a ranked output - 0 lets the step's rank kernel return at once;
+n_topk int32 @48 and topk_table_off int64 @56: how many asked for a top-k
+output and where, behind the varint chunk table, each descriptor's int32 k
+stands - both 0 and no table when nobody asked),
 descriptors {ids_off, wts_off, rows, dst_row} int64
 @64, payload @ARENA_PAYLOAD_OFF; after the last request (and any scratch) a row
 table {ids_off, wts_off} int32 per candidate row, so a GPU thread finds its
@@ -76,11 +79,13 @@ class ArenaLayout:
         return native().arena_place(arena, list(requests), start)
 
     def build(self, arena: torch.Tensor, spans: Sequence[Tuple[int, int]], ids_key="feat_ids", wts_key="feat_wts",
-              n_ranked: int = 0):
+              n_ranked: int = 0, topk: Sequence[int] = ()):
         """Parse in place + write descriptors; returns ArenaBatch (rows/offsets/errors/used_bytes).
-        ``n_ranked``: the header's count of requests that asked for a ranked output."""
+        ``n_ranked``: the header's count of requests that asked for a ranked output.
+        ``topk``: empty, or per request the k of the top-k output it asked for (0: none);
+        without a k > 0 the arena is byte for byte what it is without the argument."""
         return native().arena_build(arena, list(spans), ids_key, wts_key, self.fields, self.max_rows,
-                                    self.varint_chunks, int(n_ranked))
+                                    self.varint_chunks, int(n_ranked), [int(k) for k in topk])
 
     def unpack_cpu(self, arena: torch.Tensor, packed: torch.Tensor) -> torch.Tensor:
         native().arena_unpack_cpu(arena, packed, self.fields)

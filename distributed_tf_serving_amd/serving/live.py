@@ -112,8 +112,9 @@ class LiveScheduler:
             step_timeout_us=int(step_timeout_s * 1e6), peer_timeout_us=int(peer_timeout_s * 1e6),
             start_paused=start_paused, narrow_modulo=self.narrow_modulo, narrow_wts_cols=self.narrow_wts_cols,
             liveness_only=bool(liveness_only and control is not None),
-            caller_outputs=["sorted_prediction", "sorted_index"])  # service.RANKED_OUTPUTS
-        # ranked outputs from the step itself (ServingConfig.rank_on_gpu, local
+            # service.RANKED_OUTPUTS + service.TOP_OUTPUTS
+            caller_outputs=["sorted_prediction", "sorted_index", "top_prediction", "top_index"])
+        # ranked and top-k outputs from the step itself (ServingConfig.rank_on_gpu, local
         # steps only): the native server answers them; otherwise CALLER_PATH
         self.ranks = bool(getattr(sc, "rank_on_gpu", False)) and bool(getattr(engine, "ranks_steps", False))
         self.config["rank_outputs"] = self.ranks
@@ -141,6 +142,7 @@ class LiveScheduler:
                     from .. import ops
 
                     ops.rank_arena(self.arenas[ai], scores[slot][b], *ranked[slot][b])
+                    ops.topk_arena(self.arenas[ai], scores[slot][b], *ranked[slot][b])
 
             self.srv = native().LiveServer(self.config, self.step_rows, scores, self.arenas, forward, control, ranked)
         self.control = control

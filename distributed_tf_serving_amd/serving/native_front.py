@@ -10,10 +10,12 @@ event-loop thread that decoded it calls ``LiveServer::submit`` (validation,
 admission into the dynamic batch, one copy into the pinned arena), and the
 live server's completer hands the encoded PredictResponse back to the loop.
 The other four RPCs - and Predicts the fast path returns to its caller
-(requests larger than one batch; ranked outputs, unless the servable's step
-ranks them itself: ``ServingConfig.rank_on_gpu``, local steps, requests of at
-most 16384 rows, which the live server's completer then encodes like any
-other output) - go to
+(requests larger than one batch; ranked and top-k outputs, unless the
+servable's step produces them itself: ``ServingConfig.rank_on_gpu``, local
+steps, requests of at most 16384 rows, which go straight to
+``LiveServer::submit`` like any Predict and which the live server's completer
+then encodes like any other output; a request naming both a ``sorted_*`` and a
+``top_*`` output) - go to
 :func:`make_fallback`, which calls the same :class:`PredictionServiceImpl` as
 the grpcio door, on a few worker threads.
 

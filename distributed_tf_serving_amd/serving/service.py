@@ -8,7 +8,12 @@ All five RPCs are implemented against the model registry:
                      sorted_prediction [B] (ascending, the reference client's
                      Collections.sort, DCNClient.java:195) and sorted_index [B]
                      (the candidate permutation the reference loses), computed
-                     by the K7 bitonic sort kernel on the servable's GPU
+                     by the K7 bitonic sort kernel on the servable's GPU; and,
+                     with an input top_k (one DT_INT32 / DT_INT64 value k >= 1,
+                     shape [] or [1]), the TOP outputs top_prediction [m] and
+                     top_index [m], m = min(k, B): the m best scores,
+                     descending (ties by candidate index, NaN last), and their
+                     candidate indices
 ``Classify``         tf.Example list -> per example {label "click", score}
 ``Regress``          tf.Example list -> per example CTR value
 ``MultiInference``   several classify/regress tasks over one Example list
@@ -39,6 +44,10 @@ CLICK_LABEL = "click"
 # never pays for a sort)
 SORTED_SCORES, SORTED_INDEX = "sorted_prediction", "sorted_index"
 RANKED_OUTPUTS = (SORTED_SCORES, SORTED_INDEX)
+# top-k outputs: need the input TOP_K_INPUT; the first min(k, B) entries of the
+# descending order
+TOP_SCORES, TOP_INDEX, TOP_K_INPUT = "top_prediction", "top_index", "top_k"
+TOP_OUTPUTS = (TOP_SCORES, TOP_INDEX)
 
 
 def _dt(name: str) -> int:
@@ -74,27 +83,95 @@ class PredictionServiceImpl:
 
     def _check_filter(self, s: Servable, flt) -> None:
         for k in flt:
-            if k != s.output_key and k not in RANKED_OUTPUTS:
+            if k != s.output_key and k not in RANKED_OUTPUTS and k not in TOP_OUTPUTS:
                 raise ServingError(Code.INVALID_ARGUMENT, f"output tensor alias not found in signature: {k}")
 
-    def _outputs(self, s: Servable, flt, scores: torch.Tensor) -> List[Tuple[str, torch.Tensor]]:
+    @staticmethod
+    def _bad_top_k(why: str) -> ServingError:
+        return ServingError(Code.INVALID_ARGUMENT, f"{TOP_K_INPUT} {why}")
+
+    def _top_k_parsed(self, flt, req) -> int:
+        """The k of a natively parsed request whose filter names a top-k
+        output (0: none named; the input is then ignored like any unknown one).
+        The checks and messages are LiveServer::parse_top_k's."""
+        if not any(k in TOP_OUTPUTS for k in flt):
+            return 0
+        if not req.has_input(TOP_K_INPUT):
+            raise ServingError(Code.INVALID_ARGUMENT, f"top-k outputs need the input {TOP_K_INPUT}")
+        if req.dtype(TOP_K_INPUT) not in (pb.DT_INT32, pb.DT_INT64):
+            raise self._bad_top_k("must be DT_INT32 or DT_INT64")
+        buf = torch.zeros(1, dtype=torch.int64)
+        try:
+            shape = list(req.shape(TOP_K_INPUT))
+            if shape not in ([], [1]):
+                raise self._bad_top_k(f"must have shape [] or [1], got {shape}")
+            if req.num_values(TOP_K_INPUT) != 1:
+                raise self._bad_top_k("must hold exactly one value")
+            req.decode_into(TOP_K_INPUT, buf)
+        except ValueError as e:
+            raise self._bad_top_k(f"is malformed: {e}") from None
+        return self._checked_k(int(buf[0]))
+
+    def _top_k_message(self, flt, request) -> int:
+        """The same for a PredictRequest message."""
+        if not any(k in TOP_OUTPUTS for k in flt):
+            return 0
+        if TOP_K_INPUT not in request.inputs:
+            raise ServingError(Code.INVALID_ARGUMENT, f"top-k outputs need the input {TOP_K_INPUT}")
+        t = request.inputs[TOP_K_INPUT]
+        if t.dtype not in (pb.DT_INT32, pb.DT_INT64):
+            raise self._bad_top_k("must be DT_INT32 or DT_INT64")
+        shape = [d.size for d in t.tensor_shape.dim]
+        if t.tensor_shape.unknown_rank or shape not in ([], [1]):
+            raise self._bad_top_k(f"must have shape [] or [1], got {shape}")
+        if t.tensor_content:
+            dt = np.dtype("<i4" if t.dtype == pb.DT_INT32 else "<i8")
+            if len(t.tensor_content) != dt.itemsize:
+                raise self._bad_top_k("is malformed: tensor_content size does not match shape")
+            return self._checked_k(int(np.frombuffer(t.tensor_content, dtype=dt)[0]))
+        vals = list(t.int_val if t.dtype == pb.DT_INT32 else t.int64_val)
+        if len(vals) != 1:
+            raise self._bad_top_k("must hold exactly one value")
+        return self._checked_k(int(vals[0]))
+
+    def _checked_k(self, k: int) -> int:
+        if k < 1:
+            raise self._bad_top_k(f"must be at least 1, got {k}")
+        return k
+
+    def _outputs(self, s: Servable, flt, scores: torch.Tensor, top_k: int = 0) -> List[Tuple[str, torch.Tensor]]:
         """(key, tensor) pairs of a Predict response: prediction_node unless the
         filter names only other outputs, plus the requested ranked outputs
-        (K7 on the servable's device: ops.sort_scores)."""
+        (K7 on the servable's device: ops.sort_scores) and, with ``top_k`` (the
+        request's checked k), the requested top-k outputs (its descending form,
+        cut at min(k, B))."""
         flt = list(flt)
         out = []
         if not flt or s.output_key in flt:
             out.append((s.output_key, scores))
-        if any(k in RANKED_OUTPUTS for k in flt):
+        want_ranked = any(k in RANKED_OUTPUTS for k in flt)
+        want_top = any(k in TOP_OUTPUTS for k in flt)
+        if want_ranked or want_top:
             from .. import ops
 
             dev = getattr(getattr(s.model, "device_", None), "type", "cpu")
-            src = scores.to(s.model.device_) if dev == "cuda" else scores
-            srt, perm = ops.sort_scores(src.float())
+            src = (scores.to(s.model.device_) if dev == "cuda" else scores).float()
+        if want_ranked:
+            srt, perm = ops.sort_scores(src)
             if SORTED_SCORES in flt:
                 out.append((SORTED_SCORES, srt.cpu()))
             if SORTED_INDEX in flt:
                 out.append((SORTED_INDEX, perm.cpu().to(torch.int64)))
+        if want_top:
+            m = min(int(top_k), src.numel())
+            if m > 0:
+                top, tidx = ops.sort_scores(src, descending=True, k=m)
+            else:
+                top, tidx = src[:0], torch.empty(0, dtype=torch.int64)
+            if TOP_SCORES in flt:
+                out.append((TOP_SCORES, top.cpu()))
+            if TOP_INDEX in flt:
+                out.append((TOP_INDEX, tidx.cpu().to(torch.int64)))
         return out
 
     # ------------------------------------------------------------------ Predict (bytes, native codec)
@@ -122,19 +199,22 @@ class PredictionServiceImpl:
         rows = int(shape[0])
 
         flt = list(req.output_filter)
+        top_k = self._top_k_parsed(flt, req)
 
         def fill(ids_v, wts_v, req=req, s=s):
             req.decode_into(s.ids_key, ids_v, 0, 0)
             req.decode_into(s.wts_key, wts_v, 0, 0)
 
         fut = s.scheduler.submit(rows, fill, self._deadline_us(timeout_s))
-        return fut, (s, req.signature_name, flt)
+        return fut, (s, req.signature_name, flt, top_k)
 
     def encode_predict(self, ctx, scores: torch.Tensor, raw: bool = False) -> bytes:
         s, sig = ctx[0], ctx[1]
         flt = ctx[2] if len(ctx) > 2 else ()
+        top_k = ctx[3] if len(ctx) > 3 else 0
         return self.nat.encode_predict_response(s.name, sig or "serving_default", s.version,
-                                                [(k, t.contiguous()) for k, t in self._outputs(s, flt, scores)], raw)
+                                                [(k, t.contiguous()) for k, t in self._outputs(s, flt, scores, top_k)],
+                                                raw)
 
     def _live_fast(self):
         """The live scheduler when exactly one servable is loaded (the common
@@ -151,7 +231,7 @@ class PredictionServiceImpl:
             code, msg, resp = live.predict_raw(data, t)
             if code == 0:
                 return resp
-            # NOT_FOUND / oversize / ranked outputs: the general path resolves, splits or sorts
+            # NOT_FOUND / oversize / ranked or top-k outputs: the general path resolves, splits or sorts
             if code not in (Code.NOT_FOUND, live.OVERSIZE, live.CALLER_PATH):
                 raise ServingError(Code(code) if code in Code._value2member_map_ else Code.UNKNOWN, msg)
         fut, ctx = self.predict_async_bytes(data, timeout_s)
@@ -162,6 +242,7 @@ class PredictionServiceImpl:
         s = self._resolve(request.model_spec)
         s.signature(request.model_spec.signature_name)
         self._check_filter(s, request.output_filter)
+        top_k = self._top_k_message(request.output_filter, request)
         try:
             ids = T.to_ndarray(request.inputs[s.ids_key]) if s.ids_key in request.inputs else None
             wts = T.to_ndarray(request.inputs[s.wts_key]) if s.wts_key in request.inputs else None
@@ -172,7 +253,7 @@ class PredictionServiceImpl:
         scores = self._score(s, ids, wts, timeout_s)
         resp = pb.PredictResponse()
         self._spec_out(resp.model_spec, s, request.model_spec.signature_name)
-        for key, t in self._outputs(s, request.output_filter, scores):
+        for key, t in self._outputs(s, request.output_filter, scores, top_k):
             resp.outputs[key].CopyFrom(T.make_tensor_proto(t.numpy()))
         return resp
 
