@@ -10,8 +10,9 @@ the kernel accumulates in, and a torch.equal comparison sees it.
 Every generator is seeded, returns CPU tensors plus a float64 / int64
 reference computed with plain torch ops, and asserts the conditions under
 which the kernel is exact (they are conditions on the inputs, not tolerances).
-The parameter lists of tests/test_kernels_exact_gpu.py live here so that
-tests/test_exact_cases_cpu.py checks the same cases without a GPU.
+The parameter lists of tests/test_kernels_exact_gpu.py and
+tests/test_gather_exact_gpu.py live here so that tests/test_exact_cases_cpu.py
+checks the same cases without a GPU.
 """
 from __future__ import annotations
 
@@ -86,12 +87,12 @@ def bf16(t: torch.Tensor) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------ gather inputs
-def gather_inputs(B, F, V, modulo, seed, ids=None, wts=None):
-    """Table {-2..2} bf16 [V, 64], lin {-3..3}, weights {0, 1, 2} (the zeros
+def gather_inputs(B, F, V, modulo, seed, ids=None, wts=None, D=64):
+    """Table {-2..2} bf16 [V, D], lin {-3..3}, weights {0, 1, 2} (the zeros
     matter: padding rows and zero-weight fields stay in), int64 ids over the
     whole range including -2^63, 2^63 - 1, -1 and 0."""
-    g = _gen(1, B, F, V, seed)
-    table = _ints(g, -2, 2, (V, 64), torch.bfloat16)
+    g = _gen(1, B, F, V, seed) if D == 64 else _gen(1, B, F, V, seed, D)
+    table = _ints(g, -2, 2, (V, D), torch.bfloat16)
     lin = _ints(g, -3, 3, (V,))
     if wts is None:
         wts = _ints(g, 0, 2, (B, F))
@@ -108,7 +109,7 @@ def gather_inputs(B, F, V, modulo, seed, ids=None, wts=None):
 
 
 def embed_ref(c):
-    """float64: e [B, F, 64] = T[row] * w and the first-order sum."""
+    """float64: e [B, F, D] = T[row] * w and the first-order sum."""
     e = c.table[c.rows].double() * c.wts.double()[..., None]
     first = (c.lin[c.rows].double() * c.wts.double()).sum(1)
     return e, first
@@ -454,3 +455,300 @@ def range_case(B=200, F=43, seed=0):
     ids = pos[pick] + k * RANGE_V
     assert torch.equal(py_mod_rows(ids, RANGE_V, RANGE_V), pos[pick])
     return c, pos, ids
+
+
+# ------------------------------------------------------------------ the gather itself
+# csrc/kernels/embedding.hip through ops.embed / embed_cross / embed_fp8 /
+# embedding_bag: every embedding width, both gather kernels (one row per wave,
+# and the pipelined walk with one or two rows in flight), arena rows.
+GATHER_D = [8, 16, 32, 64, 128]
+GATHER_F = [1, 5, 43, 64, 70]  # 64 fills the wave; 70 is embed_kernel's second chunk of fields
+GATHER_B = [1, 2, 7, 67, 200]  # 7 / 67: half a pair of rows ends a two-row walk; 1 / 2: less than a block
+GATHER_V = TOWER_V
+GATHER_BIAS = -1.5
+# every D x F; B and the modulus cycle so that each meets every D and every F
+GATHER_CASES = [(GATHER_B[(i + j) % 5], F, D, TOWER_MODULI[(i + 2 * j) % 5])
+                for i, D in enumerate(GATHER_D) for j, F in enumerate(GATHER_F)]
+# (waves, rows in flight) of set_embed_wave_cap; 0 waves: the one-row-per-wave kernel
+GATHER_GEOMETRY = [(0, 1), (4, 1), (4, 2), (8, 2), (4096, 1), (4096, 2)]
+GATHER_GEOMETRY_SHAPES = [(B, 43, 64) for B in GATHER_B] + [(67, 43, D) for D in GATHER_D if D != 64]
+GATHER_ARENA_D = [16, 64, 128]
+GATHER_ARENA_GEOMETRY = [(0, 1), (4, 2), (4096, 1)]
+GATHER_FIELD_GEOMETRY = [(4, 2), (0, 1)]
+
+
+def gather_ref(c, bias=GATHER_BIAS):
+    """What ops.embed returns for the inputs ``c`` (gather_inputs, or anything
+    with table / lin / rows / wts), in float64 and then in the output types."""
+    e, first = embed_ref(c)
+    _check_gather(c, e, first)
+    # the kernels add 0.5 (S_d^2 - sum e^2) per lane to the first-order term and
+    # to the bias: every partial sum is a multiple of 0.5
+    mag = (c.lin[c.rows].abs() * c.wts).sum(1).double() + abs(bias)
+    _check_f32_sum(mag + 0.5 * (e.abs().sum(1).pow(2) + e.pow(2).sum(1)).sum(1), "fm logit", unit=0.5)
+    B = e.shape[0]
+    second = fm_term(e)
+    return SimpleNamespace(e=e, first=first, second=second, bias=bias,
+                           x=bf16(e.reshape(B, -1)),
+                           fm_bias_only=f32(torch.full((B,), bias, dtype=torch.float64)),
+                           fm_first=f32(bias + first),
+                           fm_second=f32(bias + second),
+                           fm_full=f32(bias + first + second))
+
+
+@functools.lru_cache(maxsize=64)
+def gather_case(B, F, D, modulo, seed=0, V=GATHER_V):
+    assert F <= 70, "F = 130 at D = 128 can pass 2^24 in the FM term"
+    c = gather_inputs(B, F, V, modulo, seed, D=D)
+    return c, gather_ref(c)
+
+
+def gather_case_from(ids, wts, D, V=GATHER_V, seed=0):
+    """The same for given ids / weights (arena rows), modulo V."""
+    B, F = ids.shape
+    c = gather_inputs(B, F, V, V, seed, ids=ids, wts=wts, D=D)
+    return c, gather_ref(c)
+
+
+def pad_rows(c, n):
+    """``c`` with rows n.. replaced by padding (id 0, weight 0): what an arena
+    holding the first n rows gives for c.B rows."""
+    ids, wts = c.ids.clone(), c.wts.clone()
+    ids[n:], wts[n:] = 0, 0
+    d = dict(vars(c))
+    d.update(ids=ids, wts=wts, rows=py_mod_rows(ids, c.modulo, c.V))
+    return SimpleNamespace(**d)
+
+
+# per-field tables (modulo_f / offset_f) and row shards (shard_lo_f / shard_n_f)
+GATHER_FIELD_CASES = [(67, 43, 64, True), (7, 5, 16, True), (67, 70, 128, True), (200, 64, 8, True),
+                      (67, 43, 32, False), (2, 5, 128, False)]
+_FIELD_MODULI = (1000, 1, 7, 300)
+
+
+@functools.lru_cache(maxsize=None)
+def gather_field_case(B, F, D, shards, seed=0):
+    """Field f has its own table of m_f rows at offset_f. With ``shards`` this
+    rank holds rows [lo_f, lo_f + n_f) of it - whole tables, middle halves,
+    EMPTY shards and ONE-ROW shards cycle over the fields - and an id that
+    hashes elsewhere contributes zero to x and to fm. Every third batch row
+    is planted inside the shards so that the one-row shards are hit too."""
+    g = _gen(13, B, F, D, int(shards), seed)
+    m = torch.tensor([_FIELD_MODULI[f % 4] for f in range(F)], dtype=torch.int64)
+    lo, n = torch.zeros(F, dtype=torch.int64), m.clone()
+    if shards:
+        for f in range(F):
+            mf, pat = int(m[f]), (f // 4 + f) % 4
+            if pat == 1:
+                lo[f], n[f] = mf // 4, max(mf // 2, 1)
+            elif pat == 2:
+                lo[f], n[f] = mf // 2, 0
+            elif pat == 3:
+                lo[f], n[f] = mf - 1, 1
+        assert (n == 0).any() and (n == 1).any()
+    off = torch.cumsum(torch.cat([torch.zeros(1, dtype=torch.int64), n[:-1]]), 0)
+    V = int(n.sum()) + 1  # an empty shard at the end still points at a row
+    table = _ints(g, -2, 2, (V, D), torch.bfloat16)
+    lin = _ints(g, -3, 3, (V,))
+    wts = _ints(g, 0, 2, (B, F))
+    ids = torch.randint(-(1 << 62), 1 << 62, (B, F), generator=g)
+    k = torch.randint(-(1 << 40), 1 << 40, (B, F), generator=g)
+    r = (torch.rand(B, F, generator=g) * n).long()
+    plant = (torch.arange(B) % 3 == 0)[:, None] & (n > 0)[None, :]
+    ids = torch.where(plant, lo + r + k * m, ids)
+    nedge = min(4, B * F)
+    ids.view(-1)[-nedge:] = torch.tensor(EDGE_IDS[:nedge], dtype=torch.int64)
+    h = torch.stack([py_mod_rows(ids[:, f], int(m[f]), int(m[f])) for f in range(F)], 1) - lo
+    own = (h >= 0) & (h < n)
+    rows = off + torch.where(own, h, torch.zeros_like(h))
+    assert rows.min() >= 0 and rows.max() < V
+    c = SimpleNamespace(B=B, F=F, V=V, table=table, lin=lin, ids=ids, wts_in=wts, wts=wts * own, rows=rows, own=own,
+                        modulo_f=m, offset_f=off, shard_lo_f=lo if shards else None, shard_n_f=n if shards else None)
+    if shards:
+        live = own & (wts != 0)
+        assert live[:, n == 1].any() and not own[:, n == 0].any() and (~own & (wts != 0)).any()
+    return c, gather_ref(c)
+
+
+# ------------------------------------------------------------------ cross network in the gather
+GATHER_CROSS_DF = [(64, 43), (16, 43), (32, 64)]
+GATHER_CROSS_L = [1, 3]
+GATHER_CROSS_B = 67
+CROSS_W_NNZ, CROSS_HEAD_NNZ = 8, 8
+GATHER_CROSS_LDS = 160 * 1024
+
+
+def cross_weights(F, D, L, seed=0):
+    g = _gen(14, F, D, L, seed)
+    d = F * D
+    return SimpleNamespace(w=sparse_pm1(g, L, d, CROSS_W_NNZ), hw=sparse_pm1(g, 1, d, CROSS_HEAD_NNZ)[0],
+                           b=_ints(g, -1, 1, (L, d)))
+
+
+def gather_cross_ref(c, k):
+    """ops.embed_cross on the gather inputs ``c`` with cross_weights ``k``:
+    x0 = the gathered row, x_{l+1} = x0 (x_l . w_l) + b_l + x_l, logit = x_L .
+    head_w, layer by layer in float64. The gather kernel folds the network
+    into alpha_{l+1} = alpha_l + alpha_l s_l + c_l with s_l = x0 . w_l and
+    c_l = (b_0 + .. + b_{l-1}) . w_l (ops.cross_v1_consts): those integers are
+    asserted below 2^24 too, and to give the same logit."""
+    w, hw, b = k.w, k.hw, k.b
+    L, d = w.shape
+    e, first = embed_ref(c)
+    _check_gather(c, e, first)
+    B = e.shape[0]
+    x0 = e.reshape(B, d)
+    xl = x0
+    for l in range(L):
+        _check_f32_sum(xl.abs() @ w[l].abs().double(), f"x_{l} . w_{l}")
+        xl = x0 * (xl @ w[l].double())[:, None] + b[l].double() + xl
+        _check_f32_sum(xl.abs(), f"x_{l + 1}")
+    _check_f32_sum(xl.abs() @ hw.abs().double(), "x_L . head_w")
+    logit = xl @ hw.double()
+    # the kernel's own recurrence
+    rows = torch.cat([w, hw[None]]).double()
+    beta = torch.cumsum(torch.cat([torch.zeros(1, d), b]), 0).double()
+    cc = (beta * rows).sum(1)
+    dots = x0 @ rows.t()
+    alpha = torch.ones(B, dtype=torch.float64)
+    for l in range(L):
+        for t in (alpha, alpha * dots[:, l], alpha * dots[:, l] + cc[l]):
+            _check_f32_sum(t.abs(), f"alpha step {l}")
+        alpha = alpha + alpha * dots[:, l] + cc[l]
+    _check_f32_sum(alpha.abs(), "alpha_L")
+    _check_f32_sum((alpha * dots[:, L]).abs() + cc[L].abs(), "alpha_L (x0 . head_w) + c_L")
+    assert torch.equal(alpha * dots[:, L] + cc[L], logit)
+    return SimpleNamespace(x=bf16(x0), logit=f32(logit))
+
+
+@functools.lru_cache(maxsize=None)
+def gather_cross_case(B, F, D, L, seed=0, V=GATHER_V):
+    """w_l and head_w have 8 entries of +-1, b_l is in {-1, 0, 1}; with them the
+    cases reach |logit| < 10^4 at L = 3."""
+    assert (L + 1) * F * D * 4 <= GATHER_CROSS_LDS
+    c = gather_inputs(B, F, V, V, seed + 11, D=D)
+    k = cross_weights(F, D, L, seed)
+    return c, k, gather_cross_ref(c, k)
+
+
+# ------------------------------------------------------------------ fp8 copy of the gather, row quantisation
+GATHER_FP8_CASES = [(67, 43, 64), (7, 43, 8), (200, 5, 16), (67, 64, 32), (2, 1, 128), (67, 21, 128)]
+GATHER_FP8_K_PAD = 128
+E4M3_MAX = 448.0
+
+
+def quant_rows_ref(x, k_pad=1):
+    """Per-row e4m3 quantisation of rows whose amax / 448 is a power of two and
+    whose x / scale are e4m3 values (both asserted): codes uint8 [M, K padded
+    with zeros to a multiple of k_pad], scale fp32 [M] (1 for an all-zero row)."""
+    x = x.double()
+    M, K = x.shape
+    amax = x.abs().amax(1)
+    scale = torch.where(amax > 0, amax / E4M3_MAX, torch.ones_like(amax))
+    mant, _ = torch.frexp(scale)
+    assert bool((mant == 0.5).all()), "a row's amax / 448 is not a power of two"
+    y = x / scale[:, None]
+    q = y.to(torch.float32).to(torch.float8_e4m3fn)
+    assert torch.equal(q.double(), y) and y.abs().max() <= E4M3_MAX, "x / scale is not an e4m3 value"
+    Kq = -(-K // k_pad) * k_pad
+    codes = torch.zeros(M, Kq, dtype=torch.uint8)
+    codes[:, :K] = q.view(torch.uint8)
+    return codes, f32(scale)
+
+
+@functools.lru_cache(maxsize=None)
+def gather_fp8_case(B, F, D, seed=0, V=GATHER_V):
+    """ops.embed_fp8. Table row r holds 0 or +-7 * 2^(r mod 5); weights are in
+    {0, 1, 2}. Batch row b draws its table rows from the classes j <= (2 b) mod 5
+    with the top class always present, so neighbouring rows' scales differ by
+    4x or more (a scale taken from the next row changes the codes); every
+    fifth row from the end has all weights zero (scale 1, codes 0 - or 0x80:
+    a negative entry times weight 0 is -0, in x and in its code)."""
+    g = _gen(15, B, F, D, seed)
+    cls = torch.arange(V) % 5
+    table = (_ints(g, -1, 1, (V, D)) * 7 * torch.exp2(cls.float())[:, None]).to(torch.bfloat16)
+    table[:, 0] = (7 * torch.exp2(cls.float())).to(torch.bfloat16)  # no all-zero table row
+    cap = (2 * torch.arange(B)) % 5
+    j = (torch.rand(B, F, generator=g) * (cap + 1)[:, None]).long()
+    j[torch.arange(B), torch.arange(B) % F] = cap
+    rows = j + 5 * torch.randint(0, V // 5, (B, F), generator=g)
+    assert torch.equal(rows % 5, j) and rows.max() < V
+    ids = rows + V * torch.randint(-(1 << 40), 1 << 40, (B, F), generator=g)
+    assert torch.equal(py_mod_rows(ids, V, V), rows)
+    wts = _ints(g, 0, 2, (B, F))
+    wts[torch.arange(B), torch.arange(B) % F] = _ints(g, 1, 2, (B,))
+    wts[torch.arange(B - 1, -1, -5)] = 0
+    assert (wts == 0).all(1).any()
+    c = SimpleNamespace(B=B, F=F, V=V, modulo=V, table=table, lin=None, ids=ids, wts=wts, rows=rows)
+    return c, gather_fp8_ref(c)
+
+
+def gather_fp8_ref(c):
+    e = c.table[c.rows].double() * c.wts.double()[..., None]
+    _check_bf16_ints(e, "x = T[row] * w")
+    x = bf16(e.reshape(c.B, -1))
+    codes, scale = quant_rows_ref(x, GATHER_FP8_K_PAD)
+    assert codes.shape[1] % GATHER_FP8_K_PAD == 0 and not codes[:, c.F * e.shape[2]:].any()
+    return SimpleNamespace(x=x, codes=codes, scale=scale)
+
+
+def quant_rows_views(x):
+    """Column ranges of x that ops.quant_rows_fp8 sends to quant_rows16_kernel
+    (K a multiple of 16) and to quant_rows_kernel (K = 8 mod 16). The launcher:
+    csrc/kernels/interaction.hip launch_quant_rows_fp8."""
+    K = x.shape[1]
+    k16 = K // 16 * 16
+    k8 = K if K % 16 == 8 else (K - 8 if K >= 24 else 0)
+    return [k for k in (k16, k8) if k > 0]
+
+
+# ------------------------------------------------------------------ embedding bag
+BAG_SUM_LENS = (0, 1, 3, 4, 5, 64, 65, 130)  # 65 and 130: past one wave pass (512 / D slots) for every D
+BAG_MEAN_LENS = (0, 1, 2, 4, 64, 128)  # 1 / len is a power of two
+BAG_V = 3000
+BAG_CASES = [(D, idx64, mean, out_bf16) for D in GATHER_D for idx64 in (True, False) for mean in (False, True)
+             for out_bf16 in (False, True)]
+
+
+@functools.lru_cache(maxsize=None)
+def bag_case(D, idx64, mean, out_bf16, seed=0, V=BAG_V):
+    """ops.embedding_bag: three bags of every length in a shuffled order, table
+    {-2..2}, per-sample weights {0, 1, 2} (sum pooling; mean takes none),
+    indices over the whole int64 / int32 range. bf16 output: the pooled values
+    themselves are asserted to be integers (mean: 8-bit integers / 2^k) of
+    magnitude <= 256, which they are at every length used."""
+    g = _gen(16, D, int(idx64), int(mean), int(out_bf16), seed)
+    lens = torch.tensor((BAG_MEAN_LENS if mean else BAG_SUM_LENS) * 3)
+    lens = lens[torch.randperm(lens.numel(), generator=g)]
+    offsets = torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(lens, 0)])
+    nnz = int(offsets[-1])
+    table = _ints(g, -2, 2, (V, D), torch.bfloat16)
+    bits = 62 if idx64 else 31
+    idx = torch.randint(-(1 << bits), 1 << bits, (nnz,), generator=g)
+    edge = EDGE_IDS if idx64 else (-(1 << 31), (1 << 31) - 1, -1, 0)
+    idx[:4] = torch.tensor(edge, dtype=torch.int64)
+    idx[-4:] = torch.tensor(edge, dtype=torch.int64)
+    rows = py_mod_rows(idx, V, V)
+    psw = None if mean else _ints(g, 0, 2, (nnz,))
+    c = SimpleNamespace(D=D, table=table, idx=idx if idx64 else idx.to(torch.int32), offsets=offsets, psw=psw,
+                        rows=rows, lens=lens, mean=mean, out_bf16=out_bf16, V=V)
+    return c, bag_ref(c)
+
+
+def bag_ref(c, keep=None):
+    """float64 pooling; ``keep`` (bool [nnz]) drops elements: the CPU tests' mutant."""
+    w = torch.ones(c.rows.numel(), dtype=torch.float64) if c.psw is None else c.psw.double()
+    if keep is not None:
+        w = w * keep
+    v = c.table[c.rows].double() * w[:, None]
+    out = torch.zeros(c.lens.numel(), c.D, dtype=torch.float64)
+    mag = torch.zeros_like(out)
+    bag = torch.repeat_interleave(torch.arange(c.lens.numel()), c.lens)
+    out.index_add_(0, bag, v)
+    mag.index_add_(0, bag, v.abs())
+    _check_f32_sum(mag, "bag sums")
+    if c.out_bf16:
+        _check_bf16_ints(out, "bag sums as bf16")
+    if c.mean:
+        out = out / c.lens.clamp(min=1).double()[:, None]
+    return bf16(out) if c.out_bf16 else f32(out)

@@ -17,6 +17,7 @@ from distributed_tf_serving_amd import ops
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import exact_cases as xc  # noqa: E402
+from arena_cases import arena_case as _arena_case  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -81,33 +82,6 @@ def test_gather_mlp_exact_input_forms(cuda, case):
     assert not iv.is_contiguous() and iv.dtype == torch.int32
     y = _tower(cuda, c, w, fm, act2, act3, iv, wv, modulo)
     assert torch.equal(y, want)
-
-
-def _arena_case(F, sizes, B, seed):
-    """Requests with integer weights (raw and packed-varint encodings) placed
-    in a request arena; returns the arena and the ids / weights of its B rows
-    (rows past the requests' are padding: id 0, weight 0)."""
-    from distributed_tf_serving_amd.ops import native
-    from distributed_tf_serving_amd.serving.arena import ArenaLayout
-
-    g = torch.Generator().manual_seed(seed)
-    A = ArenaLayout(F, 256)
-    ar = A.alloc()
-    reqs, ids_all, wts_all = [], [], []
-    for n, raw in sizes:
-        ids = torch.randint(-(1 << 62), 1 << 62, (n, F), generator=g)
-        ids.view(-1)[:4] = torch.tensor(xc.EDGE_IDS, dtype=torch.int64)
-        wts = torch.randint(0, 3, (n, F), generator=g).float()
-        reqs.append(native().encode_predict_request("DCN", "serving_default", None,
-                                                    [("feat_ids", ids), ("feat_wts", wts)], raw))
-        ids_all.append(ids)
-        wts_all.append(wts)
-    ab = A.build(ar, A.place(ar, reqs))
-    total = sum(n for n, _ in sizes)
-    assert not any(ab.errors) and ab.total_rows == total and ab.n_gpu_varint >= 1 and total < B
-    ids_all.append(torch.zeros(B - total, F, dtype=torch.int64))
-    wts_all.append(torch.zeros(B - total, F))
-    return A, ar, torch.cat(ids_all), torch.cat(wts_all)
 
 
 def test_gather_mlp_exact_arena_rows(cuda):
