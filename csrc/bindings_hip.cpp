@@ -981,15 +981,32 @@ static dtfs::PeerLookupArgs peer_args(const torch::Tensor& ref, const torch::Ten
   return p;
 }
 
+// fp8 peer stores (peer_lookup_fp8.hip): tscale fp32 [T], and one chunk of this
+// rank's store as the witness of the stores' dtype (the kernels see only chunk
+// addresses): e4m3 codes (or their uint8 view) [rows, 64], 8-byte aligned
+static void check_fp8_peer(const torch::Tensor& ref, const torch::Tensor& tscale, const torch::Tensor& store,
+                           int64_t T) {
+  check_same_dev(ref, tscale, "tscale");
+  check_same_dev(ref, store, "store");
+  TORCH_CHECK(store.scalar_type() == torch::kFloat8_e4m3fn || store.scalar_type() == torch::kUInt8,
+              "fp8 peer lookup: the stores must be float8_e4m3fn codes (or their uint8 view), got ",
+              store.scalar_type());
+  TORCH_CHECK(store.dim() == 2 && store.size(1) == 64 && store.is_contiguous(),
+              "fp8 peer store chunks must be contiguous [rows, 64]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(store.data_ptr()) % 8 == 0, "fp8 peer store chunks must be 8-byte aligned");
+  TORCH_CHECK(tscale.scalar_type() == torch::kFloat32 && tscale.dim() == 1 && tscale.numel() == T &&
+                  tscale.is_contiguous(),
+              "tscale must be fp32 [T], one scale per table");
+}
+
 // K1 + K5 through the peer lookup: ids [B, >= id_col0 + T] int32/int64 rows,
-// or a device request arena (B rows)
-torch::Tensor dot_interaction_gather_peer(torch::Tensor dense, c10::optional<torch::Tensor> ids,
-                                          c10::optional<torch::Tensor> arena, int64_t id_col0, torch::Tensor cbase,
-                                          torch::Tensor towner, torch::Tensor toff, torch::Tensor trows,
-                                          torch::Tensor tremote, int64_t chunk_shift,
-                                          c10::optional<torch::Tensor> cache, c10::optional<torch::Tensor> stats,
-                                          c10::optional<torch::Tensor> ring, c10::optional<torch::Tensor> ring_ctr,
-                                          int64_t sample_every, int64_t out_cols) {
+// or a device request arena (B rows). tscale / store: fp8 stores (both or neither)
+static torch::Tensor dot_interaction_gather_peer_impl(
+    torch::Tensor dense, c10::optional<torch::Tensor> ids, c10::optional<torch::Tensor> arena, int64_t id_col0,
+    torch::Tensor cbase, torch::Tensor towner, torch::Tensor toff, torch::Tensor trows, torch::Tensor tremote,
+    int64_t chunk_shift, c10::optional<torch::Tensor> cache, c10::optional<torch::Tensor> stats,
+    c10::optional<torch::Tensor> ring, c10::optional<torch::Tensor> ring_ctr, int64_t sample_every, int64_t out_cols,
+    const torch::Tensor* tscale, const torch::Tensor* store) {
   check_dev(dense, "dense");
   TORCH_CHECK(ids.has_value() != arena.has_value(), "dot_interaction_gather_peer: ids or a device arena");
   TORCH_CHECK(dense.scalar_type() == torch::kBFloat16 && dense.dim() == 2 && dense.size(1) == 64 &&
@@ -1019,6 +1036,16 @@ torch::Tensor dot_interaction_gather_peer(torch::Tensor dense, c10::optional<tor
   TORCH_CHECK(out_cols >= used && out_cols % 8 == 0 && out_cols <= 1024, "out_cols: >= used, a multiple of 8, <= 1024");
   c10::DeviceGuard g(dense.device());
   auto out = torch::empty({B, out_cols}, dense.options());
+  if (tscale) {
+    TORCH_CHECK(dense.stride(0) >= 64, "dense rows must hold 64 values");
+    check_fp8_peer(dense, *tscale, *store, T);
+    check_hip(dtfs::launch_dot_interaction_gather_peer_fp8(
+                  dense.data_ptr(), dense.stride(0), p, tscale->data_ptr<float>(), store->data_ptr(), idp, ids64, ldi,
+                  int(T), int(B), out.data_ptr(), out_cols, int(out_cols), cur_stream(dense),
+                  arena ? arena->data_ptr() : nullptr, arena ? int(id_col0) : 0),
+              "dot_interaction_gather_peer_fp8");
+    return out;
+  }
   check_hip(dtfs::launch_dot_interaction_gather(dense.data_ptr(), dense.stride(0), nullptr, 0, idp, ids64, ldi, nullptr,
                                                 nullptr, int(T), int(B), out.data_ptr(), out_cols, int(out_cols),
                                                 cur_stream(dense), arena ? arena->data_ptr() : nullptr,
@@ -1027,11 +1054,37 @@ torch::Tensor dot_interaction_gather_peer(torch::Tensor dense, c10::optional<tor
   return out;
 }
 
+torch::Tensor dot_interaction_gather_peer(torch::Tensor dense, c10::optional<torch::Tensor> ids,
+                                          c10::optional<torch::Tensor> arena, int64_t id_col0, torch::Tensor cbase,
+                                          torch::Tensor towner, torch::Tensor toff, torch::Tensor trows,
+                                          torch::Tensor tremote, int64_t chunk_shift,
+                                          c10::optional<torch::Tensor> cache, c10::optional<torch::Tensor> stats,
+                                          c10::optional<torch::Tensor> ring, c10::optional<torch::Tensor> ring_ctr,
+                                          int64_t sample_every, int64_t out_cols) {
+  return dot_interaction_gather_peer_impl(dense, ids, arena, id_col0, cbase, towner, toff, trows, tremote, chunk_shift,
+                                          cache, stats, ring, ring_ctr, sample_every, out_cols, nullptr, nullptr);
+}
+
+torch::Tensor dot_interaction_gather_peer_fp8(torch::Tensor dense, c10::optional<torch::Tensor> ids,
+                                              c10::optional<torch::Tensor> arena, int64_t id_col0, torch::Tensor cbase,
+                                              torch::Tensor towner, torch::Tensor toff, torch::Tensor trows,
+                                              torch::Tensor tremote, int64_t chunk_shift, torch::Tensor tscale,
+                                              torch::Tensor store, c10::optional<torch::Tensor> cache,
+                                              c10::optional<torch::Tensor> stats, c10::optional<torch::Tensor> ring,
+                                              c10::optional<torch::Tensor> ring_ctr, int64_t sample_every,
+                                              int64_t out_cols) {
+  return dot_interaction_gather_peer_impl(dense, ids, arena, id_col0, cbase, towner, toff, trows, tremote, chunk_shift,
+                                          cache, stats, ring, ring_ctr, sample_every, out_cols, &tscale, &store);
+}
+
 // K1b through the peer lookup: pooled bags -> out bf16 [B, T, 64]
-void peer_bag(c10::optional<torch::Tensor> ids, c10::optional<torch::Tensor> wts, c10::optional<torch::Tensor> arena,
-              int64_t B, int64_t col0, int64_t hot, torch::Tensor cbase, torch::Tensor towner, torch::Tensor toff,
-              torch::Tensor trows, torch::Tensor tremote, int64_t chunk_shift, c10::optional<torch::Tensor> cache, c10::optional<torch::Tensor> stats, c10::optional<torch::Tensor> ring,
-              c10::optional<torch::Tensor> ring_ctr, int64_t sample_every, torch::Tensor out) {
+static void peer_bag_impl(c10::optional<torch::Tensor> ids, c10::optional<torch::Tensor> wts,
+                          c10::optional<torch::Tensor> arena, int64_t B, int64_t col0, int64_t hot, torch::Tensor cbase,
+                          torch::Tensor towner, torch::Tensor toff, torch::Tensor trows, torch::Tensor tremote,
+                          int64_t chunk_shift, c10::optional<torch::Tensor> cache, c10::optional<torch::Tensor> stats,
+                          c10::optional<torch::Tensor> ring, c10::optional<torch::Tensor> ring_ctr,
+                          int64_t sample_every, torch::Tensor out, const torch::Tensor* tscale,
+                          const torch::Tensor* store) {
   check_dev(out, "out");
   TORCH_CHECK(ids.has_value() != arena.has_value(), "peer_bag: ids (+ wts) or a device arena");
   const int64_t T = trows.numel();
@@ -1065,9 +1118,36 @@ void peer_bag(c10::optional<torch::Tensor> ids, c10::optional<torch::Tensor> wts
   const auto p = peer_args(out, cbase, towner, toff, trows, tremote, chunk_shift, cache, stats, ring, ring_ctr,
                            sample_every);
   c10::DeviceGuard g(out.device());
+  if (tscale) {
+    check_fp8_peer(out, *tscale, *store, T);
+    check_hip(dtfs::launch_peer_bag_fp8(p, tscale->data_ptr<float>(), store->data_ptr(), idp, ids64, ldi, wp, ldw,
+                                        arena ? arena->data_ptr() : nullptr, int(col0), int(T), int(hot), int(B),
+                                        out.data_ptr(), cur_stream(out)),
+              "peer_bag_fp8");
+    return;
+  }
   check_hip(dtfs::launch_peer_bag(p, idp, ids64, ldi, wp, ldw, arena ? arena->data_ptr() : nullptr, int(col0), int(T),
                                   int(hot), int(B), out.data_ptr(), cur_stream(out)),
             "peer_bag");
+}
+
+void peer_bag(c10::optional<torch::Tensor> ids, c10::optional<torch::Tensor> wts, c10::optional<torch::Tensor> arena,
+              int64_t B, int64_t col0, int64_t hot, torch::Tensor cbase, torch::Tensor towner, torch::Tensor toff,
+              torch::Tensor trows, torch::Tensor tremote, int64_t chunk_shift, c10::optional<torch::Tensor> cache,
+              c10::optional<torch::Tensor> stats, c10::optional<torch::Tensor> ring,
+              c10::optional<torch::Tensor> ring_ctr, int64_t sample_every, torch::Tensor out) {
+  peer_bag_impl(ids, wts, arena, B, col0, hot, cbase, towner, toff, trows, tremote, chunk_shift, cache, stats, ring,
+                ring_ctr, sample_every, out, nullptr, nullptr);
+}
+
+void peer_bag_fp8(c10::optional<torch::Tensor> ids, c10::optional<torch::Tensor> wts,
+                  c10::optional<torch::Tensor> arena, int64_t B, int64_t col0, int64_t hot, torch::Tensor cbase,
+                  torch::Tensor towner, torch::Tensor toff, torch::Tensor trows, torch::Tensor tremote,
+                  int64_t chunk_shift, torch::Tensor tscale, torch::Tensor store, c10::optional<torch::Tensor> cache,
+                  c10::optional<torch::Tensor> stats, c10::optional<torch::Tensor> ring,
+                  c10::optional<torch::Tensor> ring_ctr, int64_t sample_every, torch::Tensor out) {
+  peer_bag_impl(ids, wts, arena, B, col0, hot, cbase, towner, toff, trows, tremote, chunk_shift, cache, stats, ring,
+                ring_ctr, sample_every, out, &tscale, &store);
 }
 
 // replica cache maintenance (parallel/hot_cache.py)
@@ -1087,6 +1167,29 @@ void peer_cache_fill(torch::Tensor keys, torch::Tensor slots, torch::Tensor cbas
   check_hip(dtfs::launch_peer_cache_fill(p, int(trows.numel()), keys.data_ptr<int64_t>(), slots.data_ptr<int32_t>(),
                                          keys.numel(), rows.data_ptr(), rows.size(0), cur_stream(rows)),
             "peer_cache_fill");
+}
+
+// the same on fp8 stores: rows = e4m3 codes (or uint8) [cap, 64], the owners' 64 code bytes verbatim
+void peer_cache_fill_fp8(torch::Tensor keys, torch::Tensor slots, torch::Tensor cbase, torch::Tensor towner,
+                         torch::Tensor toff, torch::Tensor trows, torch::Tensor tremote, int64_t chunk_shift,
+                         torch::Tensor tscale, torch::Tensor store, torch::Tensor rows) {
+  check_dev(rows, "rows");
+  for (auto* t : {&keys, &slots}) check_same_dev(rows, *t, "cache fill input");
+  TORCH_CHECK(keys.scalar_type() == torch::kInt64 && keys.is_contiguous() && slots.scalar_type() == torch::kInt32 &&
+                  slots.is_contiguous() && slots.numel() == keys.numel(),
+              "keys int64 [n], slots int32 [n]");
+  TORCH_CHECK((rows.scalar_type() == torch::kFloat8_e4m3fn || rows.scalar_type() == torch::kUInt8) && rows.dim() == 2 &&
+                  rows.size(1) == 64 && rows.is_contiguous(),
+              "fp8 peer stores: the cache rows must be contiguous float8_e4m3fn (or uint8) [cap, 64], got ",
+              rows.scalar_type());
+  check_fp8_peer(rows, tscale, store, trows.numel());
+  const auto p = peer_args(rows, cbase, towner, toff, trows, tremote, chunk_shift, c10::nullopt, c10::nullopt,
+                           c10::nullopt, c10::nullopt, 0);
+  c10::DeviceGuard g(rows.device());
+  check_hip(dtfs::launch_peer_cache_fill_fp8(p, int(trows.numel()), store.data_ptr(), keys.data_ptr<int64_t>(),
+                                             slots.data_ptr<int32_t>(), keys.numel(), rows.data_ptr(), rows.size(0),
+                                             cur_stream(rows)),
+            "peer_cache_fill_fp8");
 }
 
 void cache_index_build(torch::Tensor keys, torch::Tensor slots, torch::Tensor entries) {
@@ -2096,6 +2199,23 @@ PYBIND11_MODULE(_hip, m) {
   m.def("peer_cache_fill", &peer_cache_fill, py::arg("keys"), py::arg("slots"), py::arg("cbase"), py::arg("towner"),
         py::arg("toff"), py::arg("trows"), py::arg("tremote"), py::arg("chunk_shift"), py::arg("rows"),
         "replica cache: copy the keys' table rows into their slots");
+  m.def("dot_interaction_gather_peer_fp8", &dot_interaction_gather_peer_fp8, py::arg("dense"), py::arg("ids"),
+        py::arg("arena"), py::arg("id_col0"), py::arg("cbase"), py::arg("towner"), py::arg("toff"), py::arg("trows"),
+        py::arg("tremote"), py::arg("chunk_shift"), py::arg("tscale"), py::arg("store"),
+        py::arg("cache") = py::none(), py::arg("stats") = py::none(), py::arg("ring") = py::none(),
+        py::arg("ring_ctr") = py::none(), py::arg("sample_every") = 0, py::arg("out_cols") = 0,
+        "K1 + K5 through the peer lookup on fp8 stores: e4m3 code rows + one power-of-two scale per table "
+        "(peer_lookup_fp8.hip); store: one chunk of this rank's store (dtype witness)");
+  m.def("peer_bag_fp8", &peer_bag_fp8, py::arg("ids"), py::arg("wts"), py::arg("arena"), py::arg("B"), py::arg("col0"),
+        py::arg("hot"), py::arg("cbase"), py::arg("towner"), py::arg("toff"), py::arg("trows"), py::arg("tremote"),
+        py::arg("chunk_shift"), py::arg("tscale"), py::arg("store"), py::arg("cache") = py::none(),
+        py::arg("stats") = py::none(), py::arg("ring") = py::none(), py::arg("ring_ctr") = py::none(),
+        py::arg("sample_every") = 0, py::arg("out"),
+        "K1b multi-hot bags through the peer lookup on fp8 stores -> bf16 [B, T, 64]");
+  m.def("peer_cache_fill_fp8", &peer_cache_fill_fp8, py::arg("keys"), py::arg("slots"), py::arg("cbase"),
+        py::arg("towner"), py::arg("toff"), py::arg("trows"), py::arg("tremote"), py::arg("chunk_shift"),
+        py::arg("tscale"), py::arg("store"), py::arg("rows"),
+        "replica cache on fp8 stores: copy the keys' 64-byte code rows into their slots");
   m.def("device_alloc", &device_alloc, py::arg("nbytes"), py::arg("like"),
         "uint8 device buffer of exactly nbytes (its own hipMalloc allocation)");
   m.def("cache_index_build", &cache_index_build, py::arg("keys"), py::arg("slots"), py::arg("entries"),

@@ -260,10 +260,13 @@ hipError_t launch_cross_gemm_fp8(const CrossGemmArgs& args, hipStream_t st);
 // of rank r is at device address cbase[r * max_chunks + c]. Row v of table t
 // (v = id mod trows[t]) is row g = toff[t] + v of rank towner[t]'s store.
 // tremote[t] = 1 marks a table owned by another rank, whose rows are looked
-// up in the replica cache first. cache = device int64 [5] {index (entries
-// int64 [mask + 1][2] = {key, slot}, key -1 = empty; 0 = no index), unused,
-// mask, rows [cap][64] bf16, cap}, read by each wave at its start (the host
-// swaps indices by rewriting word 0). Candidates b with b % sample_every ==
+// up in the replica cache first. Rows are 64 bf16 (128 bytes) or, for fp8
+// tables, 64 e4m3 codes (64 bytes, peer_lookup_fp8.hip: the launchers with
+// tscale below); every rank's store and the cache rows have the same row type.
+// cache = device int64 [5] {index (entries int64 [mask + 1][2] = {key, slot},
+// key -1 = empty; 0 = no index), sample period (0: sample_every), mask, rows
+// [cap][64] of the stores' row type, cap}, read by each wave at its start (the
+// host swaps indices by rewriting word 0). Candidates b with b % sample_every ==
 // sample_every / 2 (all when sample_every <= 1) are counted - stats [128]:
 // hits at 2i, misses at 2i + 1 (i = block % 64); when sample_every > 0,
 // candidates with b % sample_every == 0 push their remote keys (t << 40 | v)
@@ -300,7 +303,8 @@ hipError_t launch_dot_interaction_gather(const void* dense, int64_t ldd, const v
 // K1 + K5 on fp8 tables (interaction_fp8.hip): the same step with table rows
 // stored as e4m3 codes [table_rows][64] and one power-of-two fp32 scale per
 // table, value = float(code) * scale[t]; bit-equal to the bf16 kernel on the
-// dequantised table. Local tables only (no peer lookup).
+// dequantised table. Local tables; sharded fp8 tables go through
+// launch_dot_interaction_gather_peer_fp8.
 hipError_t launch_dot_interaction_gather_fp8(const void* dense, int64_t ldd, const void* codes, int64_t table_rows,
                                              const float* scale, const void* ids, bool ids64, int64_t ldi,
                                              const int64_t* modulo_f, const int64_t* offset_f, int T, int B, void* out,
@@ -329,6 +333,24 @@ hipError_t launch_peer_cache_fill(const PeerLookupArgs& p, int T, const int64_t*
                                   int64_t n, void* rows, int64_t cap, hipStream_t st);
 hipError_t launch_cache_index_build(const int64_t* keys, const int32_t* slots, int64_t n, int64_t* entries,
                                     int64_t mask, hipStream_t st);
+
+// The peer lookup on fp8 tables (peer_lookup_fp8.hip): every store chunk and
+// the cache rows are e4m3 codes [rows][64] (64-byte rows), tscale fp32 [T] the
+// tables' power-of-two scales (value = float(code) * tscale[t]; never stored
+// per cache slot). Bit-equal to the three bf16 launchers above on the
+// dequantised stores; outputs stay bf16. chunk0: the base of one of this
+// rank's store chunks - the kernels read rows as 8-byte vectors, so every chunk
+// base must be 8-byte aligned (the bases live in device memory; the caller
+// that holds them on the host, parallel/hot_cache.py PeerTables, checks all).
+hipError_t launch_dot_interaction_gather_peer_fp8(const void* dense, int64_t ldd, const PeerLookupArgs& p,
+                                                  const float* tscale, const void* chunk0, const void* ids, bool ids64,
+                                                  int64_t ldi, int T, int B, void* out, int64_t ldo, int out_cols,
+                                                  hipStream_t st, const void* arena = nullptr, int id_col0 = 0);
+hipError_t launch_peer_bag_fp8(const PeerLookupArgs& p, const float* tscale, const void* chunk0, const void* ids,
+                               bool ids64, int64_t ldi, const float* wts, int64_t ldw, const void* arena, int col0,
+                               int T, int hot, int B, void* out, hipStream_t st);
+hipError_t launch_peer_cache_fill_fp8(const PeerLookupArgs& p, int T, const void* chunk0, const int64_t* keys,
+                                      const int32_t* slots, int64_t n, void* rows, int64_t cap, hipStream_t st);
 
 // K4 (small) for the DLRM bottom MLP: relu(relu(relu(pad64(bf16(wts[:, :nd]))
 // W1^T + b1) W2^T + b2) W3^T + b3) in one kernel (W1 [N1][64], W2 [N2][N1], W3

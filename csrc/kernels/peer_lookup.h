@@ -24,7 +24,7 @@ __device__ __forceinline__ uint64_t cache_hash(int64_t key, uint64_t mask) {
 struct CacheView {
   const int64_t* entries;  // [mask + 1] x {key, slot}: one 16-byte load per probe
   uint64_t mask;           // 0: the cache is empty
-  const bf16* rows;
+  const uint8_t* rows;     // [cap] rows of the store's row size (128 bytes bf16, 64 bytes e4m3 codes)
   int64_t cap;
 };
 
@@ -34,23 +34,28 @@ __device__ __forceinline__ CacheView cache_view(const PeerLookupArgs& p) {
     // the host swaps indices by rewriting the single word cache[0]
     c.entries = reinterpret_cast<const int64_t*>(p.cache[0]);
     c.mask = uint64_t(p.cache[2]);
-    c.rows = reinterpret_cast<const bf16*>(p.cache[3]);
+    c.rows = reinterpret_cast<const uint8_t*>(p.cache[3]);
     c.cap = p.cache[4];
     if (!c.entries || !c.rows || c.cap < 1) c.mask = 0;
   }
   return c;
 }
 
-// Row v of table t where it lives (its owner's store chunk)
-__device__ __forceinline__ const bf16* store_row(const PeerLookupArgs& p, int t, int64_t v) {
+// Row v of table t where it lives (its owner's store chunk). ROWB: bytes per
+// row - 128 for bf16 rows, 64 for e4m3 code rows (peer_lookup_fp8.hip).
+constexpr int kRowBytesBf16 = 128, kRowBytesFp8 = 64;
+
+template <int ROWB>
+__device__ __forceinline__ const uint8_t* store_row_bytes(const PeerLookupArgs& p, int t, int64_t v) {
   const int64_t g = p.toff[t] + v;
   const int64_t c = int64_t(p.towner[t]) * p.max_chunks + (g >> p.chunk_shift);
-  return reinterpret_cast<const bf16*>(p.cbase[c]) + (g & ((int64_t(1) << p.chunk_shift) - 1)) * 64;
+  return reinterpret_cast<const uint8_t*>(p.cbase[c]) + (g & ((int64_t(1) << p.chunk_shift) - 1)) * ROWB;
 }
 
-__device__ __forceinline__ const bf16* peer_row(const PeerLookupArgs& p, const CacheView& c, int t, int64_t v,
-                                                int& hit) {
-  const bf16* src = store_row(p, t, v);
+template <int ROWB>
+__device__ __forceinline__ const uint8_t* peer_row_bytes(const PeerLookupArgs& p, const CacheView& c, int t, int64_t v,
+                                                         int& hit) {
+  const uint8_t* src = store_row_bytes<ROWB>(p, t, v);
   hit = -1;
   if (p.tremote[t]) {
     hit = 0;
@@ -63,7 +68,7 @@ __device__ __forceinline__ const bf16* peer_row(const PeerLookupArgs& p, const C
         if (k == key) {
           const int64_t s = e[1];
           if (s >= 0 && s < c.cap) {
-            src = c.rows + s * 64;
+            src = c.rows + s * ROWB;
             hit = 1;
           }
           break;
@@ -74,6 +79,15 @@ __device__ __forceinline__ const bf16* peer_row(const PeerLookupArgs& p, const C
     }
   }
   return src;
+}
+
+// the bf16 stores' forms (interaction.hip, peer_lookup.hip)
+__device__ __forceinline__ const bf16* store_row(const PeerLookupArgs& p, int t, int64_t v) {
+  return reinterpret_cast<const bf16*>(store_row_bytes<kRowBytesBf16>(p, t, v));
+}
+__device__ __forceinline__ const bf16* peer_row(const PeerLookupArgs& p, const CacheView& c, int t, int64_t v,
+                                                int& hit) {
+  return reinterpret_cast<const bf16*>(peer_row_bytes<kRowBytesBf16>(p, c, t, v, hit));
 }
 
 // Candidates whose remote keys are sampled for the hot set (b % sample_every

@@ -14,7 +14,8 @@ Op inventory: K0 ``pack_ids``, K1 ``embed``, K1b
 ``cross_v2`` / ``linear_fp8``, K4 ``linear``, K5 ``dot_interaction``, K6
 ``head``, K4+K6 ``linear_head``, K4+K4+K6 ``mlp_tail`` / ``mlp_tail_fp8``, K7 ``sort_scores``, K7s ``rank_segments`` /
 ``rank_arena``; on fp8 tables K1+K5 ``dot_interaction_gather_fp8`` and K1b
-``embedding_bag_fp8``.
+``embedding_bag_fp8``; through the peer lookup ``dot_interaction_gather_peer`` /
+``peer_bag`` (bf16 or fp8 stores, by the peer tables' dtype).
 """
 from __future__ import annotations
 
@@ -618,17 +619,20 @@ def dot_interaction_gather_peer(dense: torch.Tensor, ids, peer, cache=None, out_
     """K1 + K5 through the peer lookup (parallel/hot_cache.py): table t's row
     of candidate b is read where it lives - this rank's store, the owner's
     store over xGMI, or this rank's replica cache of hot remote rows. ``ids``:
-    int32/int64 [B, >= id_col0 + T] rows or :class:`ArenaRows`."""
+    int32/int64 [B, >= id_col0 + T] rows or :class:`ArenaRows`. fp8 peer
+    tables (e4m3 code stores + per-table scales) take the fp8 kernel; the
+    output is bf16 either way."""
     T = peer.T
     if out_cols <= 0:
         out_cols = interaction_cols(T, dense.shape[1])
     kw = cache.kernel_args() if cache is not None else {}
     if dense.is_cuda:
+        fn = hip().dot_interaction_gather_peer
+        if peer.fp8:
+            fn, kw = hip().dot_interaction_gather_peer_fp8, dict(kw, store=peer.mine)
         if isinstance(ids, ArenaRows):
-            return hip().dot_interaction_gather_peer(dense, None, ids.arena, int(id_col0), out_cols=int(out_cols),
-                                                     **peer.kernel_args(), **kw)
-        return hip().dot_interaction_gather_peer(dense, _rows(ids), None, int(id_col0), out_cols=int(out_cols),
-                                                 **peer.kernel_args(), **kw)
+            return fn(dense, None, ids.arena, int(id_col0), out_cols=int(out_cols), **peer.kernel_args(), **kw)
+        return fn(dense, _rows(ids), None, int(id_col0), out_cols=int(out_cols), **peer.kernel_args(), **kw)
     from ..parallel.hot_cache import peer_gather_cpu
 
     if isinstance(ids, ArenaRows):
@@ -641,18 +645,20 @@ def peer_bag(ids, wts: Optional[torch.Tensor], B: int, col0: int, hot: int, peer
              out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """K1b through the peer lookup: bf16 [B, T, 64] pooled bags (table t's bag =
     columns col0 + t * hot .. + hot - 1 of ``ids`` / ``wts``, or of the
-    :class:`ArenaRows`)."""
+    :class:`ArenaRows`). fp8 peer tables pool dequantised rows; bf16 out."""
     T = peer.T
     dev = peer.trows.device
     if out is None:
-        out = torch.empty(B, T, 64, dtype=peer.dtype, device=dev)
+        out = torch.empty(B, T, 64, dtype=torch.bfloat16 if peer.fp8 else peer.dtype, device=dev)
     kw = cache.kernel_args() if cache is not None else {}
     if dev.type == "cuda":
+        fn = hip().peer_bag
+        if peer.fp8:
+            fn, kw = hip().peer_bag_fp8, dict(kw, store=peer.mine)
         if isinstance(ids, ArenaRows):
-            hip().peer_bag(None, None, ids.arena, int(B), int(col0), int(hot), out=out, **peer.kernel_args(), **kw)
+            fn(None, None, ids.arena, int(B), int(col0), int(hot), out=out, **peer.kernel_args(), **kw)
         else:
-            hip().peer_bag(_rows(ids), _rows(wts.float()), None, int(B), int(col0), int(hot), out=out,
-                           **peer.kernel_args(), **kw)
+            fn(_rows(ids), _rows(wts.float()), None, int(B), int(col0), int(hot), out=out, **peer.kernel_args(), **kw)
         return out
     from ..parallel.hot_cache import peer_gather_cpu
 

@@ -25,7 +25,10 @@ parallelism (collective C3):
     exchange at all - each rank maps its peers' stores (IPC) and the lookup
     loads every row where it lives over xGMI, hot remote rows from a per-rank
     replica cache refreshed from online counts (parallel/hot_cache.py); the
-    bytes crossing xGMI are the cache misses x 128.
+    bytes crossing xGMI are the cache misses x 128. ``table_dtype: fp8``
+    (this exchange only, > 1 rank): the stores are 64-byte rows of e4m3 codes
+    with one power-of-two scale per table held on every rank - half the
+    shard, misses x 64, and a cached row costs 160 bytes in place of 224.
 * **`ShardedDLRM`**: the DLRM forward with sharded tables; dense towers are
   replicated and run data-parallel over each rank's candidates.
 
@@ -162,7 +165,8 @@ def plan_sharding(tables: Sequence[TableSpec], world: int, budget_bytes: int = i
 
 
 def dlrm_tables(cfg: ModelConfig) -> List[TableSpec]:
-    eb = torch.tensor([], dtype=DTYPES[cfg.param_dtype]).element_size()
+    dt = torch.float8_e4m3fn if getattr(cfg, "table_dtype", "bf16") == "fp8" else DTYPES[cfg.param_dtype]
+    eb = torch.tensor([], dtype=dt).element_size()
     return [TableSpec(f"t{f}", cfg.table_rows, cfg.embed_dim, eb) for f in range(cfg.num_sparse)]
 
 
@@ -189,12 +193,21 @@ class ShardedEmbedding(nn.Module):
 
     def __init__(self, plan: ShardingPlan, ctx: DistContext, seed: int, bound: float, dtype=torch.bfloat16,
                  device="cpu", group=None, col_base: int = 0, hot: int = 1, exchange: str = "alltoall",
-                 cache_rows: int = 0, cache_sample_every: int = 8):
+                 cache_rows: int = 0, cache_sample_every: int = 8, table_dtype: str = "bf16"):
         super().__init__()
         self.plan, self.ctx, self.group = plan, ctx, group
         self.world, self.rank = plan.world, ctx.rank if plan.world > 1 else 0
         if exchange not in ("alltoall", "peer"):
             raise ValueError(f"unknown embedding exchange {exchange!r}")
+        if table_dtype not in ("bf16", "fp8"):
+            raise ValueError(f"table_dtype must be bf16 or fp8, got {table_dtype!r}")
+        # fp8: the store chunks are e4m3 codes, scale [T] their tables' scales;
+        # only the peer lookup reads them (the all-to-all ships bf16 rows)
+        self.table_fp8 = table_dtype == "fp8"
+        if self.table_fp8 and (exchange != "peer" or plan.row_wise()):
+            raise ValueError("fp8 tables shard table-wise behind the peer exchange only (exchange='peer', "
+                             "policy='table')")
+        self.out_dtype = dtype  # looked-up rows and exchange buffers (bf16 also over an fp8 store)
         self.exchange = exchange
         self.col_base = int(col_base)
         # multi-hot: table t's ids are columns col_base + t * hot .. + hot - 1,
@@ -239,20 +252,36 @@ class ShardedEmbedding(nn.Module):
             tok: list = [None] * self.world
             dist.all_gather_object(tok, uuid.uuid4().hex[:12], group=group)
             shm_tag = f"/dev/shm/dtfs_peer_{tok[0]}_{self.rank}"
+        store_dtype = torch.float8_e4m3fn if self.table_fp8 else dtype
         if peer:
             # chunks of 8 M rows, each its own allocation (GPU: its own IPC
             # object - a peer maps exactly that chunk)
-            chunks = hot_cache.alloc_store(self.rows_local, dtype, dev, shm_tag)
+            chunks = hot_cache.alloc_store(self.rows_local, store_dtype, dev, shm_tag)
         else:
-            chunks = [torch.empty(max(1, self.rows_local), self.D, dtype=dtype, device=dev)]
+            chunks = [torch.empty(max(1, self.rows_local), self.D, dtype=store_dtype, device=dev)]
         per = chunks[0].shape[0]
+        scale = None
+        if self.table_fp8:
+            # as DLRM._init_fp8_tables fills emb_q: the hashed init through a bf16
+            # scratch of <= 2^19 rows, quantised piece by piece with the scale of
+            # the init's bound - byte for byte the unsharded fp8 model's rows, and
+            # the full bf16 shard never exists
+            scale = ops_k.table_scale_fp8(torch.full((T,), float(bound)))
+            piece = max(1, min(1 << 19, per))
+            scratch = torch.empty(piece, self.D, dtype=dtype, device=dev)
         for t, s, n, o in self.segments:  # each segment's rows, chunk by chunk
             r = o
             while r < o + n:
                 c, i = divmod(r, per)
                 k = min(o + n - r, chunks[c].shape[0] - i)
-                hashed_uniform_rows_(chunks[c][i:i + k], t, s + (r - o), seed, bound)
+                if self.table_fp8:
+                    k = min(k, piece)
+                    hashed_uniform_rows_(scratch[:k], t, s + (r - o), seed, bound)
+                    chunks[c][i:i + k] = ops_k.quant_table_fp8(scratch[:k], float(scale[t]))
+                else:
+                    hashed_uniform_rows_(chunks[c][i:i + k], t, s + (r - o), seed, bound)
                 r += k
+        self.register_buffer("emb_scale", None if scale is None else scale.to(dev), persistent=False)
         self.store = nn.Parameter(chunks[0], requires_grad=False)
         # the other chunks (peer exchange with > 8 M local rows)
         self.store_chunks = nn.ParameterList([nn.Parameter(c, requires_grad=False) for c in chunks[1:]])
@@ -268,7 +297,8 @@ class ShardedEmbedding(nn.Module):
             owner = [next(r for r in range(self.world) if t in self.tw_by_rank[r]) for t in range(T)]
             self.peer = hot_cache.PeerTables(stores, owner, [lay[owner[t]][1][t] for t in range(T)],
                                              [plan.tables[t].rows for t in range(T)], self.rank,
-                                             chunk_shift=hot_cache.CHUNK_SHIFT if peer else None)
+                                             chunk_shift=hot_cache.CHUNK_SHIFT if peer else None,
+                                             scale=self.emb_scale)
             if peer and cache_rows != 0 and self.peer.remote_tables:  # < 0: sized from free HBM
                 self.cache = hot_cache.HotRowCache(self.peer, cache_rows, sample_every=cache_sample_every)
         i64 = dict(dtype=torch.int64, device=dev)
@@ -315,6 +345,16 @@ class ShardedEmbedding(nn.Module):
         p.stores = [chunks if r == self.rank else [] for r, chunks in enumerate(p.stores)]
         self.peers_released = True
 
+    def set_table_scale(self, scale: torch.Tensor) -> None:
+        """Install the per-table scales of an fp8 store (checkpoint load), in
+        place: captured steps keep reading the same buffers."""
+        if not self.table_fp8 or scale.numel() != self.T:
+            raise ValueError("set_table_scale needs an fp8 store and one scale per table")
+        self.emb_scale.copy_(scale.to(self.emb_scale.device))
+        if self.peer is not None:
+            self.peer.scale.copy_(self.emb_scale)
+            self.peer.scale_cpu.copy_(self.emb_scale.cpu())
+
     def local_bytes(self) -> int:
         return sum(c.numel() * c.element_size() for c in [self.store, *self.store_chunks])
 
@@ -328,7 +368,7 @@ class ShardedEmbedding(nn.Module):
         and the lookup writes straight into ``emb_all`` (no collectives)."""
         dev, W, tm, D, Tr, hot = self.store.device, self.world, self.tmax, self.D, len(self.rw), self.hot
         i32 = dict(dtype=torch.int32, device=dev)
-        bf = dict(dtype=self.store.dtype, device=dev)
+        bf = dict(dtype=self.out_dtype, device=dev)
         nt = self.n_tw_rows(B)
         bufs = {"emb_all": torch.zeros(max(1, nt + B * Tr), D, **bf)}
         if self.tw_tables:
@@ -350,7 +390,8 @@ class ShardedEmbedding(nn.Module):
         """Bytes this rank sends to OTHER ranks per step (ids + weights out,
         embeddings back): what crosses xGMI. Peer exchange: the rows this
         rank loads from peers with no replica cache (every remote lookup);
-        the cache's counters give the measured bytes (misses x 128)."""
+        the cache's counters give the measured bytes (misses x 128; x 64 on
+        an fp8 store, whose element size this already reflects)."""
         W, tm, D, Tr, hot = self.world, self.tmax, self.D, len(self.rw), self.hot
         if W == 1:
             return 0
@@ -389,6 +430,8 @@ class ShardedEmbedding(nn.Module):
         :class:`ops.ArenaRows` - the route kernel then reads ids and weights
         straight from the request bytes (K0 fused into the routing)."""
         W, tm, D, Tr, hot = self.world, self.tmax, self.D, len(self.rw), self.hot
+        if self.table_fp8:
+            raise ValueError("fp8 tables are read by the peer lookup only (no route / gather / all-to-all program)")
         ops: List[sp.Op] = []
 
         def route():
@@ -459,10 +502,19 @@ def peer_access_everywhere(ctx: DistContext, device: torch.device, group=None) -
     return all(votes)
 
 
-def _reject_fp8_tables(cfg: ModelConfig) -> None:
-    if getattr(cfg, "table_dtype", "bf16") != "bf16":
-        raise ValueError(f"table_dtype: {cfg.table_dtype} tables are single-rank only: the sharded and peer "
-                         "lookups read bf16 rows (serve the model unsharded, or use table_dtype: bf16)")
+def _reject_fp8_tables(cfg: ModelConfig, world: int = 1) -> None:
+    """fp8 tables shard in exactly one combination: embedding_exchange set to
+    "peer" explicitly ("auto" may resolve to the all-to-all, whose RCCL path
+    ships bf16 rows) on more than one rank."""
+    if getattr(cfg, "table_dtype", "bf16") == "bf16":
+        return
+    exchange = getattr(cfg, "embedding_exchange", "alltoall")
+    if exchange == "peer" and world > 1:
+        return
+    raise ValueError(f"table_dtype: {cfg.table_dtype} tables are single-rank only, except sharded table-wise with "
+                     f"embedding_exchange: peer on more than one rank (got embedding_exchange: {exchange}, "
+                     f"{world} rank{'s' if world != 1 else ''}): the all-to-all and RCCL lookups ship bf16 rows "
+                     "(serve the model unsharded, use embedding_exchange: peer, or table_dtype: bf16)")
 
 
 def build_parallel_model(cfg: ModelConfig, device, ctx: Optional[DistContext] = None, shard_tables: str = "auto",
@@ -475,7 +527,7 @@ def build_parallel_model(cfg: ModelConfig, device, ctx: Optional[DistContext] = 
 
     ctx = ctx or DistContext(device=torch.device(device))
     if cfg.family == "dlrm" and (shard_tables == "on" or (shard_tables == "auto" and ctx.is_distributed)):
-        _reject_fp8_tables(cfg)
+        _reject_fp8_tables(cfg, ctx.world if ctx.is_distributed else 1)
         return ShardedDLRM(cfg, ctx, device=device, policy=policy, budget_bytes=budget_bytes, group=group).eval()
     return build_model(cfg, device)
 
@@ -495,10 +547,10 @@ class ShardedDLRM(nn.Module):
     def __init__(self, cfg: ModelConfig, ctx: DistContext, device="cpu", plan: Optional[ShardingPlan] = None,
                  policy: str = "auto", budget_bytes: int = int(0.8 * MI355X_HBM_BYTES), group=None):
         super().__init__()
-        _reject_fp8_tables(cfg)
+        world = ctx.world if ctx.is_distributed else 1
+        _reject_fp8_tables(cfg, world)
         self.cfg, self.ctx, self.group = cfg, ctx, group
         self.hot = max(1, int(getattr(cfg, "multi_hot", 1)))
-        world = ctx.world if ctx.is_distributed else 1
         exchange = getattr(cfg, "embedding_exchange", "alltoall")
         if exchange == "auto":
             exchange = "peer" if peer_access_everywhere(ctx, torch.device(device), group) else "alltoall"
@@ -511,7 +563,8 @@ class ShardedDLRM(nn.Module):
         self.dense.gen = None
         self.emb = ShardedEmbedding(self.plan, ctx, cfg.seed, self.dense.table_bound, DTYPES[cfg.param_dtype],
                                     device, group, col_base=cfg.num_dense, hot=self.hot, exchange=exchange,
-                                    cache_rows=int(getattr(cfg, "hot_cache_rows", -1)))
+                                    cache_rows=int(getattr(cfg, "hot_cache_rows", -1)),
+                                    table_dtype=getattr(cfg, "table_dtype", "bf16"))
         self.device_ = torch.device(device)
 
     def signature(self):
@@ -523,7 +576,7 @@ class ShardedDLRM(nn.Module):
     def alloc(self, B: int) -> Dict[str, torch.Tensor]:
         if self._peer_step():
             e = self.emb
-            return {"emb_all": torch.zeros(B * e.T, e.D, dtype=e.store.dtype, device=e.store.device)} if self.hot > 1 \
+            return {"emb_all": torch.zeros(B * e.T, e.D, dtype=e.out_dtype, device=e.store.device)} if self.hot > 1 \
                 else {}
         return self.emb.alloc(B)
 

@@ -19,7 +19,9 @@ a full replica, reference ``README.md``). The exchange mode of
   rows of tables owned by OTHER ranks in HBM left over after its shard
   (288 GB per GPU), behind an open-addressing index; the lookup probes it
   first and goes over xGMI only on a miss, so the bytes crossing xGMI per step
-  are ``misses x 128``. The hot set comes from online counts: the kernel pushes
+  are ``misses x 128`` - ``misses x 64`` on fp8 tables, whose stores and
+  cache rows are 64-byte rows of e4m3 codes (``PeerTables(..., scale=...)``,
+  csrc/kernels/peer_lookup_fp8.hip). The hot set comes from online counts: the kernel pushes
   the remote keys of every ``sample_every``-th candidate into a ring, and
   :meth:`HotRowCache.refresh` (a background thread in serving, or called
   between steps) folds the ring into exponentially decayed counts, picks the
@@ -62,10 +64,14 @@ class PeerTables:
     rank's own, a peer's mapped by IPC (GPU: each chunk is its own allocation
     and its own IPC object), or views of a peer's shared-memory file (CPU). A
     rank given as one tensor is one chunk. Table t is rows ``off[t] ..
-    off[t] + rows[t]`` of ``stores[owner[t]]``."""
+    off[t] + rows[t]`` of ``stores[owner[t]]``.
+
+    fp8 tables (``table_dtype: fp8``): every chunk of every rank holds
+    ``float8_e4m3fn`` codes and ``scale`` (fp32 [T], powers of two, the same on
+    every rank) gives table t's values as ``float(code) * scale[t]``."""
 
     def __init__(self, stores: Sequence, owner: Sequence[int], off: Sequence[int], rows: Sequence[int], rank: int,
-                 chunk_shift: Optional[int] = None):
+                 chunk_shift: Optional[int] = None, scale: Optional[torch.Tensor] = None):
         self.stores = [[s] if isinstance(s, torch.Tensor) else list(s) for s in stores]
         self.owner, self.off, self.rows, self.rank = list(owner), list(off), list(rows), int(rank)
         self.T = len(self.owner)
@@ -91,6 +97,22 @@ class PeerTables:
         mine = self.stores[self.rank][0]
         dev = mine.device
         self.dtype = mine.dtype
+        self.mine = mine  # the fp8 kernels' witness of the stores' dtype (they see only chunk addresses)
+        if any(c.dtype != self.dtype for chunks in self.stores for c in chunks):
+            raise ValueError("peer stores must have one dtype on every rank, got "
+                             f"{sorted({str(c.dtype) for chunks in self.stores for c in chunks})}")
+        self.fp8 = self.dtype == torch.float8_e4m3fn
+        if self.fp8 != (scale is not None):
+            raise ValueError("fp8 peer stores (float8_e4m3fn codes) need scale [T] and scale needs fp8 stores: got "
+                             f"{self.dtype} stores " + ("with" if scale is not None else "without") + " a scale")
+        self.scale = self.scale_cpu = None
+        if self.fp8:
+            if scale.numel() != self.T:
+                raise ValueError(f"scale must hold one value per table: {scale.numel()} for {self.T} tables")
+            if any(c.data_ptr() % 8 for chunks in self.stores for c in chunks):
+                raise ValueError("fp8 peer store chunks must be 8-byte aligned")
+            self.scale_cpu = scale.detach().float().cpu().reshape(-1).contiguous()
+            self.scale = self.scale_cpu.to(dev)
         maxc = max(len(c) for c in self.stores)
         i64 = dict(dtype=torch.int64, device=dev)
         self.trows = torch.tensor(self.rows, **i64)
@@ -105,15 +127,19 @@ class PeerTables:
         self.tremote_cpu = self.tremote.cpu().bool()
 
     def kernel_args(self) -> dict:
-        return dict(cbase=self.cbase, towner=self.towner, toff=self.toff, trows=self.trows, tremote=self.tremote,
-                    chunk_shift=self.chunk_shift)
+        kw = dict(cbase=self.cbase, towner=self.towner, toff=self.toff, trows=self.trows, tremote=self.tremote,
+                  chunk_shift=self.chunk_shift)
+        if self.fp8:
+            kw["tscale"] = self.scale
+        return kw
 
     @property
     def remote_tables(self) -> int:
         return int(self.tremote_cpu.sum())
 
     def row_cpu(self, t: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
-        """Rows v of tables t (int64 [n] each) read from their owners' stores."""
+        """Rows v of tables t (int64 [n] each) read from their owners' stores
+        (raw rows in the store dtype: codes for fp8 tables)."""
         out = torch.empty(t.numel(), D, dtype=self.dtype)
         own = self._owner_cpu[t]
         g = self._off_cpu[t] + v
@@ -125,11 +151,24 @@ class PeerTables:
             out[m] = self.stores[k >> 20][k & ((1 << 20) - 1)][local[m]].cpu()
         return out
 
+    def values_cpu(self, rows: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
+        """fp32 values of raw rows [n, 64] (store or cache) of tables t: the
+        rows themselves, codes x ``scale[t]`` for fp8 tables (exact)."""
+        if not self.fp8:
+            return rows.float()
+        return rows.float() * self.scale_cpu[t].unsqueeze(-1)
+
 
 # Bytes of device memory one cached row costs: the bf16 row + its share of the
 # two {key, slot} index buffers (2 x 2 entries x 16 B at the 50 % load factor)
-# + the hot-set / candidate arrays of a refresh.
-CACHE_BYTES_PER_ROW = 2 * D + 64 + 32
+# + the hot-set / candidate arrays of a refresh. fp8 tables: cache_bytes_per_row.
+CACHE_OVERHEAD_PER_ROW = 64 + 32
+CACHE_BYTES_PER_ROW = 2 * D + CACHE_OVERHEAD_PER_ROW
+
+
+def cache_bytes_per_row(dtype) -> int:
+    """CACHE_BYTES_PER_ROW for rows of ``dtype``: 224 for bf16, 160 for e4m3 codes."""
+    return D * torch.tensor([], dtype=dtype).element_size() + CACHE_OVERHEAD_PER_ROW
 
 
 def auto_capacity(peer: "PeerTables", free_bytes: Optional[int] = None, fraction: float = 0.25,
@@ -145,7 +184,7 @@ def auto_capacity(peer: "PeerTables", free_bytes: Optional[int] = None, fraction
     if free_bytes is None:
         dev = peer.trows.device
         free_bytes = torch.cuda.mem_get_info(dev)[0] if dev.type == "cuda" else 1 << 30
-    fit = int(fraction * free_bytes) // CACHE_BYTES_PER_ROW
+    fit = int(fraction * free_bytes) // cache_bytes_per_row(peer.dtype)
     return max(min(floor, remote_rows), min(remote_rows, fit))
 
 
@@ -164,7 +203,8 @@ def _member(x: torch.Tensor, sorted_set: torch.Tensor) -> torch.Tensor:
 class HotRowCache:
     """This rank's replica of hot rows of tables owned by other ranks.
 
-    ``capacity`` rows ([capacity, 64] bf16) behind two open-addressing index
+    ``capacity`` rows ([capacity, 64] in the stores' dtype: bf16, or the
+    owners' e4m3 code bytes verbatim for fp8 tables) behind two open-addressing index
     buffers ({key, slot} int64 entries [H, 2], H = the power of two >= 2 x
     capacity; one 16-byte load per probe): one serves the steps while
     :meth:`refresh` rebuilds the other.
@@ -395,7 +435,10 @@ class HotRowCache:
         if self.device.type == "cuda":
             from ..ops import hip
 
-            hip().peer_cache_fill(keys, slots, rows=self.rows, **p.kernel_args())
+            if p.fp8:
+                hip().peer_cache_fill_fp8(keys, slots, rows=self.rows, store=p.mine, **p.kernel_args())
+            else:
+                hip().peer_cache_fill(keys, slots, rows=self.rows, **p.kernel_args())
         else:
             t, v = keys >> KEY_SHIFT, keys & ROW_MASK
             self.rows[slots.long()] = p.row_cpu(t, v)
@@ -450,18 +493,20 @@ def peer_gather_cpu(peer: PeerTables, cache: Optional[HotRowCache], ids: torch.T
                     hot: int) -> torch.Tensor:
     """CPU reference of the peer lookup (kernels/peer_lookup.h): ids [B, T *
     hot] (table t's bag = columns t * hot .. + hot - 1), wts the same shape for
-    bags (None: one-hot) -> bf16 [B, T, 64]; counts and samples like the kernels."""
+    bags (None: one-hot) -> bf16 [B, T, 64]; counts and samples like the
+    kernels. fp8 tables: rows from stores and cache alike are dequantised with
+    their table's scale before pooling; the result is bf16."""
     B, T = ids.shape[0], peer.T
     t = torch.arange(T, dtype=torch.int64).repeat_interleave(hot).view(1, -1).expand(B, -1).reshape(-1)
     v = torch.remainder(ids.long().reshape(-1), peer.trows_cpu[t])
-    rows = peer.row_cpu(t, v).float()
+    rows = peer.values_cpu(peer.row_cpu(t, v), t)
     if cache is not None:
         remote = peer.tremote_cpu[t]
         keys = (t << KEY_SHIFT) | v
         slot = cache.lookup_cpu(keys)
         hit = remote & (slot >= 0)
         if bool(hit.any()):
-            rows[hit] = cache.rows.cpu()[slot[hit]].float()
+            rows[hit] = peer.values_cpu(cache.rows.cpu()[slot[hit]], t[hit])
         b = torch.arange(B, dtype=torch.int64).repeat_interleave(T * hot)
         n = cache.sample_every
         sp = cache.sample_period if cache.sample_period > 0 else n  # the kernels' peer_sample_period
@@ -474,7 +519,7 @@ def peer_gather_cpu(peer: PeerTables, cache: Optional[HotRowCache], ids: torch.T
         out = rows.view(B, T, D)
     else:
         out = (rows.view(B, T, hot, D) * wts.float().reshape(B, T, hot, 1)).sum(2)
-    return out.to(peer.dtype)
+    return out.to(torch.bfloat16 if peer.fp8 else peer.dtype)
 
 
 def open_peer_stores(chunks: List[torch.Tensor], group=None, shm_tag: Optional[str] = None,
@@ -509,7 +554,12 @@ def open_peer_stores(chunks: List[torch.Tensor], group=None, shm_tag: Optional[s
         elif cuda:
             from ..ops import hip
 
-            out.append([hip().ipc_open(h, off, shape, chunks[0]) for h, off, shape in theirs])
+            like = chunks[0]
+            if like.dtype == torch.float8_e4m3fn:  # codes cross IPC as bytes and are re-viewed
+                out.append([hip().ipc_open(h, off, shape, like.view(torch.uint8)).view(like.dtype)
+                            for h, off, shape in theirs])
+            else:
+                out.append([hip().ipc_open(h, off, shape, like) for h, off, shape in theirs])
         else:
             path, _, shape = theirs[0]
             whole = torch.from_file(path, shared=True, size=int(shape[0]) * D, dtype=chunks[0].dtype).view(*shape)

@@ -15,7 +15,10 @@ the file).
   that rank's table shards keyed by (table, first global row), plus the dense
   towers on rank 0, and a JSON manifest of every shard. Loading re-slices rows
   from whichever files hold them, so a checkpoint written by N ranks loads on
-  M ranks (re-sharding).
+  M ranks (re-sharding). fp8 tables (``table_dtype: fp8`` behind the peer
+  exchange): the shards are the uint8 code rows, the per-table scales are the
+  manifest's ``emb_scale``, and ``table_dtype`` (in ``model_config``) must
+  match the model loaded into.
 """
 from __future__ import annotations
 
@@ -67,10 +70,21 @@ def read_config(path: str) -> ModelConfig:
 
 
 # ---------------------------------------------------------------- sharded DLRM
-def _bf16_tables_only(cfg: ModelConfig) -> None:
-    # fp8 tables (table_dtype: fp8) are single-rank: save_model / load_model round-trip emb_q + emb_scale
-    if getattr(cfg, "table_dtype", "bf16") != "bf16":
-        raise ValueError("sharded checkpoints hold bf16 table rows; use save_model / load_model for fp8 tables")
+def _table_dtype(cfg) -> str:
+    return getattr(cfg, "table_dtype", "bf16") if not isinstance(cfg, dict) else cfg.get("table_dtype", "bf16")
+
+
+def _store_pieces(emb, lo: int, hi: int):
+    """Store rows [lo, hi) as (first row, view) pieces, one per store chunk they
+    touch; fp8 code rows as their uint8 bytes."""
+    base = 0
+    for c in [emb.store, *emb.store_chunks]:
+        n = c.shape[0]
+        a, b = max(lo, base), min(hi, base + n)
+        if a < b:
+            v = c.data[a - base:b - base]
+            yield a, v.view(torch.uint8) if v.dtype == torch.float8_e4m3fn else v
+        base += n
 
 
 def _shard_key(table: int, lo: int) -> str:
@@ -81,7 +95,6 @@ def save_sharded(model, path: str) -> None:
     """Collective over the model's process group: every rank writes its file."""
     import torch.distributed as dist
 
-    _bf16_tables_only(model.cfg)
     emb = model.emb
     rank, world = emb.rank, emb.world
     os.makedirs(path, exist_ok=True)
@@ -89,7 +102,7 @@ def save_sharded(model, path: str) -> None:
     for t, lo, n, off in emb.segments:
         if n == 0:
             continue
-        tensors[_shard_key(t, lo)] = emb.store[off:off + n].detach().contiguous().cpu()
+        tensors[_shard_key(t, lo)] = torch.cat([v.detach().cpu() for _, v in _store_pieces(emb, off, off + n)])
         shards.append({"table": t, "lo": lo, "rows": n, "file": f"rank{rank}.safetensors"})
     if rank == 0:
         for k, v in _state(model.dense).items():
@@ -103,6 +116,8 @@ def save_sharded(model, path: str) -> None:
     if rank == 0:
         manifest = {"world": world, "shards": [s for part in all_shards for s in part],
                     "model_config": json.loads(_cfg_meta(model.cfg)["model_config"])}
+        if _table_dtype(model.cfg) == "fp8":
+            manifest["emb_scale"] = [float(x) for x in emb.emb_scale.cpu().tolist()]  # powers of two: exact in JSON
         with open(os.path.join(path, MANIFEST), "w") as f:
             json.dump(manifest, f, indent=1)
     if world > 1 and dist.is_initialized():
@@ -111,11 +126,13 @@ def save_sharded(model, path: str) -> None:
 
 def load_sharded(model, path: str) -> None:
     """Fill this rank's shards (any saved world size) and the dense towers."""
-    _bf16_tables_only(model.cfg)
     with open(os.path.join(path, MANIFEST)) as f:
         manifest = json.load(f)
-    if manifest.get("model_config", {}).get("table_dtype", "bf16") != "bf16":
-        raise ValueError("sharded checkpoints hold bf16 table rows; this one was written with fp8 tables")
+    saved, mine = _table_dtype(manifest.get("model_config", {})), _table_dtype(model.cfg)
+    if saved != mine:
+        raise ValueError(f"this sharded checkpoint holds {saved} table rows; the model has table_dtype: {mine}")
+    if mine == "fp8" and len(manifest.get("emb_scale", [])) != model.emb.T:
+        raise ValueError("fp8 sharded checkpoint without one emb_scale per table in its manifest")
     by_table: Dict[int, List[dict]] = {}
     for s in manifest["shards"]:
         by_table.setdefault(s["table"], []).append(s)
@@ -136,10 +153,14 @@ def load_sharded(model, path: str) -> None:
                 if a >= b:
                     continue
                 rows = h(s["file"]).get_slice(_shard_key(t, s["lo"]))[a - s["lo"]:b - s["lo"]]
-                emb.store[off + a - lo:off + b - lo].copy_(rows)
+                first = off + a - lo
+                for r0, v in _store_pieces(emb, first, off + b - lo):
+                    v.copy_(rows[r0 - first:r0 - first + v.shape[0]])
                 filled += b - a
             if filled != n:
                 raise ValueError(f"checkpoint covers {filled} of table {t}'s rows [{lo}, {lo + n})")
+        if mine == "fp8":
+            emb.set_table_scale(torch.tensor(manifest["emb_scale"], dtype=torch.float32))
         f0 = h("rank0.safetensors")
         dense = {k[len("dense."):]: f0.get_tensor(k) for k in f0.keys() if k.startswith("dense.")}
         model.dense.load_state_dict(dense, strict=True)

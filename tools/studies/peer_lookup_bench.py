@@ -8,6 +8,8 @@ interaction of 16384 candidates x 26 one-hot tables, rows gathered
 
 On one GPU the "remote" store is local HBM, so this measures the lookup's own
 overhead (chunk addressing, cache probes, counters, sampling), not xGMI.
+``--table-dtype fp8``: the same three on e4m3 code stores with per-table
+scales (``local`` is then ``dot_interaction_gather_fp8``).
 Prints one JSON line."""
 from __future__ import annotations
 
@@ -25,6 +27,7 @@ def main() -> None:
     ap.add_argument("--batch", type=int, default=16384)
     ap.add_argument("--cache-rows", type=int, default=1 << 20)
     ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--table-dtype", choices=("bf16", "fp8"), default="bf16")
     a = ap.parse_args()
     from distributed_tf_serving_amd import ops
     from distributed_tf_serving_amd.client.synth import SyntheticRequests
@@ -36,14 +39,26 @@ def main() -> None:
     # rank 0 owns tables [0, half), "rank 1" the rest; both stores on this GPU
     own = [0 if t < half else 1 for t in range(T)]
     n0, n1 = half * R, (T - half) * R
-    stores = [alloc_store(n0, torch.bfloat16, dev), alloc_store(n1, torch.bfloat16, dev)]
+    fp8 = a.table_dtype == "fp8"
+    sdt = torch.float8_e4m3fn if fp8 else torch.bfloat16
+    # fp8: finite positive codes (< 0x78) x 2^-12 per table: values of the bf16 run's magnitude
+    scale = torch.full((T,), 2.0 ** -12, device=dev) if fp8 else None
+
+    def fill(x):
+        if fp8:
+            x.view(torch.uint8).random_(0, 0x78)
+        else:
+            x.uniform_(-0.05, 0.05)
+
+    stores = [alloc_store(n0, sdt, dev), alloc_store(n1, sdt, dev)]
     for chunks in stores:
         for c in chunks:
-            c.uniform_(-0.05, 0.05)
+            fill(c)
     off = [t * R if t < half else (t - half) * R for t in range(T)]
-    peer = PeerTables(stores, own, off, [R] * T, rank=0, chunk_shift=CHUNK_SHIFT)
+    peer = PeerTables(stores, own, off, [R] * T, rank=0, chunk_shift=CHUNK_SHIFT, scale=scale)
     # the local form: every table in one [T x R, 64] store (separate buffer, same values not needed)
-    local = torch.empty(T * R, 64, dtype=torch.bfloat16, device=dev).uniform_(-0.05, 0.05)
+    local = torch.empty(T * R, 64, dtype=sdt, device=dev)
+    fill(local)
     modf = torch.full((T,), R, dtype=torch.int64, device=dev)
     offf = torch.arange(T, dtype=torch.int64, device=dev) * R
     synth = SyntheticRequests(fields=T, id_space=1 << 40, dist="zipf", seed=5)
@@ -62,8 +77,11 @@ def main() -> None:
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) * 1e3 / a.iters
 
-    out = {"batch": B, "tables": T, "rows_per_table": R, "remote_tables": T - half}
-    out["local_us"] = round(timed(lambda ids: ops.dot_interaction_gather(dense, local, ids, modf, offf)), 2)
+    out = {"table_dtype": a.table_dtype, "batch": B, "tables": T, "rows_per_table": R, "remote_tables": T - half}
+    if fp8:
+        out["local_us"] = round(timed(lambda ids: ops.dot_interaction_gather_fp8(dense, local, scale, ids, modf, offf)), 2)
+    else:
+        out["local_us"] = round(timed(lambda ids: ops.dot_interaction_gather(dense, local, ids, modf, offf)), 2)
     out["peer_us"] = round(timed(lambda ids: ops.dot_interaction_gather_peer(dense, ids, peer)), 2)
     cache = HotRowCache(peer, a.cache_rows, sample_every=8)
     for _ in range(4):  # learn the stream
@@ -76,13 +94,14 @@ def main() -> None:
     from distributed_tf_serving_amd.ops import hip
 
     # the same lookups without the counters / sampling, and the counters alone
-    out["peer_cache_no_counters_us"] = round(timed(lambda ids: hip().dot_interaction_gather_peer(
-        dense, ids, None, 0, cache=cache.desc, **peer.kernel_args())), 2)
-    out["peer_counters_only_us"] = round(timed(lambda ids: hip().dot_interaction_gather_peer(
-        dense, ids, None, 0, stats=cache.stats, ring=cache.ring, ring_ctr=cache.ring_ctr, sample_every=8,
-        **peer.kernel_args())), 2)
-    out["peer_stats_only_us"] = round(timed(lambda ids: hip().dot_interaction_gather_peer(
-        dense, ids, None, 0, stats=cache.stats, **peer.kernel_args())), 2)
+    raw = hip().dot_interaction_gather_peer
+    pk = peer.kernel_args()
+    if fp8:
+        raw, pk = hip().dot_interaction_gather_peer_fp8, dict(pk, store=peer.mine)
+    out["peer_cache_no_counters_us"] = round(timed(lambda ids: raw(dense, ids, None, 0, cache=cache.desc, **pk)), 2)
+    out["peer_counters_only_us"] = round(timed(lambda ids: raw(
+        dense, ids, None, 0, stats=cache.stats, ring=cache.ring, ring_ctr=cache.ring_ctr, sample_every=8, **pk)), 2)
+    out["peer_stats_only_us"] = round(timed(lambda ids: raw(dense, ids, None, 0, stats=cache.stats, **pk)), 2)
     out["hit_rate"] = round(h / max(1, h + m), 4)
     out["hot_rows"] = int(cache.keys.numel())
     # the same hot set on a fresh draw of the stream

@@ -4,6 +4,8 @@ exactly as 8 GPUs do over xGMI): the sharded DLRM reading every table where it
 lives scores like the unsharded DLRM of the same seed - one-hot (the fused
 interaction kernel) and multi-hot bags - before and after the hot-row replica
 cache fills, through the eager forward and through the arena step program.
+``--table-dtype fp8``: both models hold fp8 tables (e4m3 code stores behind
+the peer lookup against the unsharded fp8 DLRM of the same seed).
 Rank 0 prints one JSON line."""
 from __future__ import annotations
 
@@ -20,6 +22,7 @@ def main() -> int:
     ap.add_argument("--rows", type=int, default=20011)
     ap.add_argument("--batch", type=int, default=2048)
     ap.add_argument("--hot", type=int, default=1)
+    ap.add_argument("--table-dtype", choices=("bf16", "fp8"), default="bf16")
     a = ap.parse_args()
     from distributed_tf_serving_amd import ops
     from distributed_tf_serving_amd.client.synth import SyntheticRequests
@@ -38,14 +41,15 @@ def main() -> int:
 
     T = 8
     cfg = ModelConfig(family="dlrm", num_fields=13 + T * a.hot, num_dense=13, table_rows=a.rows, embed_dim=64,
-                      multi_hot=a.hot, embedding_exchange="peer", hot_cache_rows=4096)
+                      multi_hot=a.hot, embedding_exchange="peer", hot_cache_rows=4096,
+                      table_dtype=a.table_dtype)
     m = ShardedDLRM(cfg, ctx, device=dev)
     ref = build_model(cfg, dev)  # the unsharded DLRM, same seed
     cache = m.cache
     assert cache is not None and not m.has_collectives
     cache.sample_every = 1
     synth = SyntheticRequests(fields=cfg.num_fields, id_space=1 << 40, dist="zipf", seed=17 + ctx.rank)
-    res = {"world": ctx.world, "hot": a.hot, "remote_tables": m.emb.peer.remote_tables, "rounds": []}
+    res = {"world": ctx.world, "hot": a.hot, "table_dtype": a.table_dtype, "remote_tables": m.emb.peer.remote_tables, "rounds": []}
     F = cfg.num_fields
     for rnd in range(3):
         ids_np, wts_np = synth.arrays(a.batch)
