@@ -922,6 +922,38 @@ torch::Tensor shard_route(c10::optional<torch::Tensor> ids, c10::optional<torch:
 }
 
 // ---------------------------------------------------------------- peer lookup
+// the replica cache's side of PeerLookupArgs
+static void peer_cache_args(dtfs::PeerLookupArgs& p, const torch::Tensor& ref,
+                            const c10::optional<torch::Tensor>& cache, const c10::optional<torch::Tensor>& stats,
+                            const c10::optional<torch::Tensor>& ring, const c10::optional<torch::Tensor>& ring_ctr,
+                            int64_t sample_every) {
+  if (cache) {
+    check_same_dev(ref, *cache, "cache");
+    TORCH_CHECK(cache->scalar_type() == torch::kInt64 && cache->numel() == 5 && cache->is_contiguous(), "cache: int64 [5]");
+    p.cache = cache->data_ptr<int64_t>();
+  }
+  if (stats) {
+    check_same_dev(ref, *stats, "stats");
+    TORCH_CHECK(stats->scalar_type() == torch::kInt64 && stats->numel() == 128 && stats->is_contiguous(),
+                "stats: int64 [128]");
+    p.stats = reinterpret_cast<unsigned long long*>(stats->data_ptr<int64_t>());
+  }
+  if (ring) {
+    TORCH_CHECK(ring_ctr.has_value(), "ring needs ring_ctr");
+    check_same_dev(ref, *ring, "ring");
+    check_same_dev(ref, *ring_ctr, "ring_ctr");
+    TORCH_CHECK(ring->scalar_type() == torch::kInt64 && ring->numel() >= 64 && ring->numel() % 64 == 0 &&
+                    ring->is_contiguous(),
+                "ring: int64 [cap], cap a multiple of 64");
+    TORCH_CHECK(ring_ctr->scalar_type() == torch::kInt64 && ring_ctr->numel() == 64 && ring_ctr->is_contiguous(),
+                "ring_ctr: int64 [64]");
+    p.ring = ring->data_ptr<int64_t>();
+    p.ring_ctr = reinterpret_cast<unsigned long long*>(ring_ctr->data_ptr<int64_t>());
+    p.ring_cap = ring->numel();
+    p.sample_every = int(std::max<int64_t>(sample_every, 0));
+  }
+}
+
 // PeerTables (parallel/hot_cache.py): cbase int64 [W * max_chunks] (device
 // addresses of every rank's store chunks), towner int32 [T], toff int64 [T],
 // trows int64 [T], tremote int32 [T]; the replica cache: cache int64 [5],
@@ -953,31 +985,7 @@ static dtfs::PeerLookupArgs peer_args(const torch::Tensor& ref, const torch::Ten
   p.chunk_shift = int(chunk_shift);
   p.max_chunks = int(cbase.size(-1));
   TORCH_CHECK(cbase.dim() == 2, "cbase must be [W, max_chunks]");
-  if (cache) {
-    check_same_dev(ref, *cache, "cache");
-    TORCH_CHECK(cache->scalar_type() == torch::kInt64 && cache->numel() == 5 && cache->is_contiguous(), "cache: int64 [5]");
-    p.cache = cache->data_ptr<int64_t>();
-  }
-  if (stats) {
-    check_same_dev(ref, *stats, "stats");
-    TORCH_CHECK(stats->scalar_type() == torch::kInt64 && stats->numel() == 128 && stats->is_contiguous(),
-                "stats: int64 [128]");
-    p.stats = reinterpret_cast<unsigned long long*>(stats->data_ptr<int64_t>());
-  }
-  if (ring) {
-    TORCH_CHECK(ring_ctr.has_value(), "ring needs ring_ctr");
-    check_same_dev(ref, *ring, "ring");
-    check_same_dev(ref, *ring_ctr, "ring_ctr");
-    TORCH_CHECK(ring->scalar_type() == torch::kInt64 && ring->numel() >= 64 && ring->numel() % 64 == 0 &&
-                    ring->is_contiguous(),
-                "ring: int64 [cap], cap a multiple of 64");
-    TORCH_CHECK(ring_ctr->scalar_type() == torch::kInt64 && ring_ctr->numel() == 64 && ring_ctr->is_contiguous(),
-                "ring_ctr: int64 [64]");
-    p.ring = ring->data_ptr<int64_t>();
-    p.ring_ctr = reinterpret_cast<unsigned long long*>(ring_ctr->data_ptr<int64_t>());
-    p.ring_cap = ring->numel();
-    p.sample_every = int(std::max<int64_t>(sample_every, 0));
-  }
+  peer_cache_args(p, ref, cache, stats, ring, ring_ctr, sample_every);
   return p;
 }
 
@@ -1190,6 +1198,209 @@ void peer_cache_fill_fp8(torch::Tensor keys, torch::Tensor slots, torch::Tensor 
                                              slots.data_ptr<int32_t>(), keys.numel(), rows.data_ptr(), rows.size(0),
                                              cur_stream(rows)),
             "peer_cache_fill_fp8");
+}
+
+// ---- the peer lookup through row ranges (peer_lookup_rows.hip)
+// The range descriptor, checked once on the host and then kept on the device:
+// the row-wise launches below take only this object, so no launch can address
+// outside a store through ranges nobody checked. rlo int64 [T, W + 1], roff
+// int64 [T, W], trows int64 [T], store_rows int64 [W] (every rank's store
+// rows) are CPU tensors; cbase is PeerTables' device tensor [W, max_chunks].
+struct PeerRowRanges {
+  torch::Tensor cbase, rlo, roff, trows;  // device
+  int64_t T = 0, world = 0, rank = 0, chunk_shift = 0;
+};
+
+static std::shared_ptr<PeerRowRanges> peer_row_ranges(torch::Tensor cbase, torch::Tensor rlo, torch::Tensor roff,
+                                                      torch::Tensor trows, torch::Tensor store_rows, int64_t rank,
+                                                      int64_t chunk_shift) {
+  check_dev(cbase, "cbase");
+  TORCH_CHECK(cbase.scalar_type() == torch::kInt64 && cbase.dim() == 2 && cbase.is_contiguous() && cbase.size(1) >= 1,
+              "cbase must be contiguous int64 [W, max_chunks]");
+  const int64_t W = cbase.size(0), maxc = cbase.size(1);
+  TORCH_CHECK(W >= 1 && W <= 64 && rank >= 0 && rank < W, "row ranges: 1 <= world <= 64 and 0 <= rank < world, got world ",
+              W, " rank ", rank);
+  TORCH_CHECK(chunk_shift >= 1 && chunk_shift <= 40, "chunk_shift in [1, 40]");
+  for (auto* t : {&rlo, &roff, &trows, &store_rows})
+    TORCH_CHECK(t->device().is_cpu() && t->scalar_type() == torch::kInt64 && t->is_contiguous(),
+                "row ranges: rlo / roff / trows / store_rows must be contiguous int64 CPU tensors");
+  const int64_t T = trows.numel();
+  TORCH_CHECK(T >= 1 && trows.dim() == 1, "row ranges: trows int64 [T], T >= 1");
+  TORCH_CHECK(rlo.dim() == 2 && rlo.size(0) == T && rlo.size(1) == W + 1, "row ranges: rlo must be int64 [T, world + 1] = [",
+              T, ", ", W + 1, "]");
+  TORCH_CHECK(roff.dim() == 2 && roff.size(0) == T && roff.size(1) == W, "row ranges: roff must be int64 [T, world] = [", T,
+              ", ", W, "]");
+  TORCH_CHECK(store_rows.dim() == 1 && store_rows.numel() == W, "row ranges: store_rows must be int64 [world]: cbase has ",
+              W, " rows");
+  const auto cb = cbase.cpu();
+  const int64_t *lo = rlo.data_ptr<int64_t>(), *of = roff.data_ptr<int64_t>(), *tr = trows.data_ptr<int64_t>(),
+                *sr = store_rows.data_ptr<int64_t>(), *cbp = cb.data_ptr<int64_t>();
+  for (int64_t t = 0; t < T; ++t) {
+    const int64_t* l = lo + t * (W + 1);
+    TORCH_CHECK(tr[t] >= 1 && tr[t] < (int64_t(1) << 40), "row ranges: table ", t, " has ", tr[t], " rows");
+    TORCH_CHECK(l[0] == 0 && l[W] == tr[t], "row ranges: table ", t, " must run from 0 to its ", tr[t], " rows, got ", l[0],
+                " .. ", l[W]);
+    for (int64_t r = 0; r < W; ++r) {
+      const int64_t n = l[r + 1] - l[r], o = of[t * W + r];
+      TORCH_CHECK(n >= 0, "row ranges: table ", t, " starts decrease at rank ", r + 1);
+      TORCH_CHECK(o >= 0 && sr[r] >= 0 && o + n <= sr[r], "row ranges: table ", t, " rank ", r, ": store rows ", o, " .. ",
+                  o + n, " outside the rank's store (", sr[r], " rows)");
+      if (n == 0) continue;
+      const int64_t c0 = o >> chunk_shift, c1 = (o + n - 1) >> chunk_shift;
+      TORCH_CHECK(c1 < maxc, "row ranges: table ", t, " rank ", r, " reaches chunk ", c1, " of ", maxc);
+      for (int64_t c = c0; c <= c1; ++c)
+        TORCH_CHECK(cbp[r * maxc + c] != 0, "row ranges: rank ", r, " chunk ", c, " is not mapped");
+    }
+  }
+  auto d = std::make_shared<PeerRowRanges>();
+  d->cbase = cbase;
+  d->rlo = rlo.to(cbase.device());
+  d->roff = roff.to(cbase.device());
+  d->trows = trows.to(cbase.device());
+  d->T = T;
+  d->world = W;
+  d->rank = rank;
+  d->chunk_shift = chunk_shift;
+  return d;
+}
+
+// peer_args' sibling for the range descriptor
+static dtfs::PeerLookupArgs peer_args_rows(const torch::Tensor& ref, const PeerRowRanges& d,
+                                           const c10::optional<torch::Tensor>& cache,
+                                           const c10::optional<torch::Tensor>& stats,
+                                           const c10::optional<torch::Tensor>& ring,
+                                           const c10::optional<torch::Tensor>& ring_ctr, int64_t sample_every) {
+  check_same_dev(ref, d.cbase, "peer row ranges");
+  dtfs::PeerLookupArgs p;
+  p.cbase = d.cbase.data_ptr<int64_t>();
+  p.trows = d.trows.data_ptr<int64_t>();
+  p.rlo = d.rlo.data_ptr<int64_t>();
+  p.roff = d.roff.data_ptr<int64_t>();
+  p.world = int(d.world);
+  p.rank = int(d.rank);
+  p.chunk_shift = int(d.chunk_shift);
+  p.max_chunks = int(d.cbase.size(1));
+  peer_cache_args(p, ref, cache, stats, ring, ring_ctr, sample_every);
+  return p;
+}
+
+// tscale + store together (fp8 stores) or neither (bf16 stores)
+static bool rows_fp8(const torch::Tensor& ref, const c10::optional<torch::Tensor>& tscale,
+                     const c10::optional<torch::Tensor>& store, int64_t T) {
+  TORCH_CHECK(tscale.has_value() == store.has_value(), "row-wise peer lookup: tscale and store go together (fp8 stores)");
+  if (tscale) check_fp8_peer(ref, *tscale, *store, T);
+  return tscale.has_value();
+}
+
+torch::Tensor dot_interaction_gather_peer_rows(torch::Tensor dense, c10::optional<torch::Tensor> ids,
+                                               c10::optional<torch::Tensor> arena, int64_t id_col0,
+                                               const PeerRowRanges& desc, c10::optional<torch::Tensor> tscale,
+                                               c10::optional<torch::Tensor> store, c10::optional<torch::Tensor> cache,
+                                               c10::optional<torch::Tensor> stats, c10::optional<torch::Tensor> ring,
+                                               c10::optional<torch::Tensor> ring_ctr, int64_t sample_every,
+                                               int64_t out_cols) {
+  check_dev(dense, "dense");
+  TORCH_CHECK(ids.has_value() != arena.has_value(), "dot_interaction_gather_peer_rows: ids or a device arena");
+  TORCH_CHECK(dense.scalar_type() == torch::kBFloat16 && dense.dim() == 2 && dense.size(1) == 64 &&
+                  dense.stride(1) == 1 && dense.stride(0) % 8 == 0 && dense.stride(0) >= 64,
+              "dense must be bf16 [B, 64] with unit inner stride");
+  const int64_t B = dense.size(0), T = desc.T;
+  TORCH_CHECK(T >= 1 && T + 1 <= 32 && id_col0 >= 0, "1 <= T <= 31 tables, id_col0 >= 0");
+  const void* idp = nullptr;
+  bool ids64 = true;
+  int64_t ldi = 0;
+  if (ids) {
+    check_same_dev(dense, *ids, "ids");
+    TORCH_CHECK((ids->scalar_type() == torch::kInt64 || ids->scalar_type() == torch::kInt32) && ids->dim() == 2 &&
+                    ids->stride(1) == 1 && ids->size(0) == B && ids->size(1) >= id_col0 + T,
+                "ids must be int32/int64 [B, >= id_col0 + T] rows with unit inner stride");
+    ids64 = ids->scalar_type() == torch::kInt64;
+    ldi = ids->stride(0);
+    idp = static_cast<const uint8_t*>(ids->data_ptr()) + id_col0 * ids->element_size();
+  } else {
+    check_same_dev(dense, *arena, "arena");
+    TORCH_CHECK(arena->scalar_type() == torch::kUInt8 && arena->is_contiguous(), "arena must be a contiguous uint8 buffer");
+  }
+  const auto p = peer_args_rows(dense, desc, cache, stats, ring, ring_ctr, sample_every);
+  const bool fp8 = rows_fp8(dense, tscale, store, T);
+  const int64_t used = 64 + (T + 1) * T / 2;
+  if (out_cols <= 0) out_cols = (used + 7) / 8 * 8;
+  TORCH_CHECK(out_cols >= used && out_cols % 8 == 0 && out_cols <= 1024, "out_cols: >= used, a multiple of 8, <= 1024");
+  c10::DeviceGuard g(dense.device());
+  auto out = torch::empty({B, out_cols}, dense.options());
+  check_hip(dtfs::launch_dot_interaction_gather_peer_rows(
+                dense.data_ptr(), dense.stride(0), p, fp8 ? tscale->data_ptr<float>() : nullptr,
+                fp8 ? store->data_ptr() : nullptr, idp, ids64, ldi, int(T), int(B), out.data_ptr(), out_cols,
+                int(out_cols), cur_stream(dense), arena ? arena->data_ptr() : nullptr, arena ? int(id_col0) : 0),
+            "dot_interaction_gather_peer_rows");
+  return out;
+}
+
+void peer_bag_rows(c10::optional<torch::Tensor> ids, c10::optional<torch::Tensor> wts,
+                   c10::optional<torch::Tensor> arena, int64_t B, int64_t col0, int64_t hot, const PeerRowRanges& desc,
+                   c10::optional<torch::Tensor> tscale, c10::optional<torch::Tensor> store,
+                   c10::optional<torch::Tensor> cache, c10::optional<torch::Tensor> stats,
+                   c10::optional<torch::Tensor> ring, c10::optional<torch::Tensor> ring_ctr, int64_t sample_every,
+                   torch::Tensor out) {
+  check_dev(out, "out");
+  TORCH_CHECK(ids.has_value() != arena.has_value(), "peer_bag_rows: ids (+ wts) or a device arena");
+  const int64_t T = desc.T;
+  TORCH_CHECK(T >= 1 && hot >= 1 && col0 >= 0 && B >= 0, "T, hot >= 1, col0 >= 0");
+  TORCH_CHECK(out.scalar_type() == torch::kBFloat16 && out.is_contiguous() && out.numel() == B * T * 64,
+              "out must be contiguous bf16 [B, T, 64]");
+  const void* idp = nullptr;
+  const float* wp = nullptr;
+  bool ids64 = true;
+  int64_t ldi = 0, ldw = 0;
+  const int64_t need = col0 + T * hot;
+  if (ids) {
+    TORCH_CHECK(wts.has_value(), "peer_bag_rows: ids need wts");
+    check_same_dev(out, *ids, "ids");
+    check_same_dev(out, *wts, "wts");
+    TORCH_CHECK((ids->scalar_type() == torch::kInt64 || ids->scalar_type() == torch::kInt32) && ids->dim() == 2 &&
+                    ids->stride(1) == 1 && ids->size(0) == B && ids->size(1) >= need,
+                "ids must be int32/int64 [B, >= col0 + T * hot] rows with unit inner stride");
+    TORCH_CHECK(wts->scalar_type() == torch::kFloat32 && wts->dim() == 2 && wts->stride(1) == 1 && wts->size(0) == B &&
+                    wts->size(1) >= need,
+                "wts must be fp32 [B, >= col0 + T * hot] rows with unit inner stride");
+    ids64 = ids->scalar_type() == torch::kInt64;
+    idp = ids->data_ptr();
+    ldi = ids->stride(0);
+    wp = wts->data_ptr<float>();
+    ldw = wts->stride(0);
+  } else {
+    check_same_dev(out, *arena, "arena");
+    TORCH_CHECK(arena->scalar_type() == torch::kUInt8 && arena->is_contiguous(), "arena must be a contiguous uint8 buffer");
+  }
+  const auto p = peer_args_rows(out, desc, cache, stats, ring, ring_ctr, sample_every);
+  const bool fp8 = rows_fp8(out, tscale, store, T);
+  c10::DeviceGuard g(out.device());
+  check_hip(dtfs::launch_peer_bag_rows(p, fp8 ? tscale->data_ptr<float>() : nullptr, fp8 ? store->data_ptr() : nullptr,
+                                       idp, ids64, ldi, wp, ldw, arena ? arena->data_ptr() : nullptr, int(col0), int(T),
+                                       int(hot), int(B), out.data_ptr(), cur_stream(out)),
+            "peer_bag_rows");
+}
+
+void peer_cache_fill_rows(torch::Tensor keys, torch::Tensor slots, const PeerRowRanges& desc,
+                          c10::optional<torch::Tensor> tscale, c10::optional<torch::Tensor> store, torch::Tensor rows) {
+  check_dev(rows, "rows");
+  for (auto* t : {&keys, &slots}) check_same_dev(rows, *t, "cache fill input");
+  TORCH_CHECK(keys.scalar_type() == torch::kInt64 && keys.is_contiguous() && slots.scalar_type() == torch::kInt32 &&
+                  slots.is_contiguous() && slots.numel() == keys.numel(),
+              "keys int64 [n], slots int32 [n]");
+  const bool fp8 = rows_fp8(rows, tscale, store, desc.T);
+  TORCH_CHECK(rows.dim() == 2 && rows.size(1) == 64 && rows.is_contiguous(), "cache rows must be contiguous [cap, 64]");
+  TORCH_CHECK(fp8 ? rows.scalar_type() == torch::kFloat8_e4m3fn || rows.scalar_type() == torch::kUInt8
+                  : rows.scalar_type() == torch::kBFloat16,
+              fp8 ? "fp8 peer stores: the cache rows must be float8_e4m3fn (or uint8) [cap, 64], got "
+                  : "rows must be contiguous bf16 [cap, 64], got ",
+              rows.scalar_type());
+  const auto p = peer_args_rows(rows, desc, c10::nullopt, c10::nullopt, c10::nullopt, c10::nullopt, 0);
+  c10::DeviceGuard g(rows.device());
+  check_hip(dtfs::launch_peer_cache_fill_rows(p, int(desc.T), fp8, fp8 ? store->data_ptr() : nullptr,
+                                              keys.data_ptr<int64_t>(), slots.data_ptr<int32_t>(), keys.numel(),
+                                              rows.data_ptr(), rows.size(0), cur_stream(rows)),
+            "peer_cache_fill_rows");
 }
 
 void cache_index_build(torch::Tensor keys, torch::Tensor slots, torch::Tensor entries) {
@@ -2216,6 +2427,33 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("towner"), py::arg("toff"), py::arg("trows"), py::arg("tremote"), py::arg("chunk_shift"),
         py::arg("tscale"), py::arg("store"), py::arg("rows"),
         "replica cache on fp8 stores: copy the keys' 64-byte code rows into their slots");
+  py::class_<PeerRowRanges, std::shared_ptr<PeerRowRanges>>(
+      m, "PeerRowRanges", "a checked range descriptor of row-wise sharded peer tables, held on the device")
+      .def_readonly("rlo", &PeerRowRanges::rlo)
+      .def_readonly("roff", &PeerRowRanges::roff)
+      .def_readonly("trows", &PeerRowRanges::trows)
+      .def_readonly("cbase", &PeerRowRanges::cbase)
+      .def_readonly("world", &PeerRowRanges::world)
+      .def_readonly("rank", &PeerRowRanges::rank)
+      .def_readonly("chunk_shift", &PeerRowRanges::chunk_shift);
+  m.def("peer_row_ranges", &peer_row_ranges, py::arg("cbase"), py::arg("rlo"), py::arg("roff"), py::arg("trows"),
+        py::arg("store_rows"), py::arg("rank"), py::arg("chunk_shift"),
+        "check row ranges (CPU int64 rlo [T, W + 1], roff [T, W], trows [T], store_rows [W]) against the stores "
+        "and keep them on cbase's device");
+  m.def("dot_interaction_gather_peer_rows", &dot_interaction_gather_peer_rows, py::arg("dense"), py::arg("ids"),
+        py::arg("arena"), py::arg("id_col0"), py::arg("desc"), py::arg("tscale") = py::none(),
+        py::arg("store") = py::none(), py::arg("cache") = py::none(), py::arg("stats") = py::none(),
+        py::arg("ring") = py::none(), py::arg("ring_ctr") = py::none(), py::arg("sample_every") = 0,
+        py::arg("out_cols") = 0,
+        "K1 + K5 through the peer lookup on row-wise sharded tables (peer_lookup_rows.hip); tscale + store: fp8 stores");
+  m.def("peer_bag_rows", &peer_bag_rows, py::arg("ids"), py::arg("wts"), py::arg("arena"), py::arg("B"),
+        py::arg("col0"), py::arg("hot"), py::arg("desc"), py::arg("tscale") = py::none(), py::arg("store") = py::none(),
+        py::arg("cache") = py::none(), py::arg("stats") = py::none(), py::arg("ring") = py::none(),
+        py::arg("ring_ctr") = py::none(), py::arg("sample_every") = 0, py::arg("out"),
+        "K1b multi-hot bags through the peer lookup on row-wise sharded tables -> bf16 [B, T, 64]");
+  m.def("peer_cache_fill_rows", &peer_cache_fill_rows, py::arg("keys"), py::arg("slots"), py::arg("desc"),
+        py::arg("tscale") = py::none(), py::arg("store") = py::none(), py::arg("rows"),
+        "replica cache on row-wise sharded tables: copy the keys' rows into their slots");
   m.def("device_alloc", &device_alloc, py::arg("nbytes"), py::arg("like"),
         "uint8 device buffer of exactly nbytes (its own hipMalloc allocation)");
   m.def("cache_index_build", &cache_index_build, py::arg("keys"), py::arg("slots"), py::arg("entries"),

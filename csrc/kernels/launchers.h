@@ -286,6 +286,17 @@ struct PeerLookupArgs {
   unsigned long long* ring_ctr = nullptr;
   int64_t ring_cap = 0;
   int sample_every = 0;
+  // the range descriptor (row-wise and mixed plans, peer_lookup_rows.hip):
+  // rlo int64 [T][world + 1], the cumulative range starts of each table
+  // (rlo[t][0] = 0, non-decreasing, rlo[t][world] = trows[t]); roff int64
+  // [T][world], the row of rank r's store where its range of table t begins.
+  // Row v of table t is store row roff[t][r] + (v - rlo[t][r]) of the one rank
+  // r with rlo[t][r] <= v < rlo[t][r + 1], remote iff r != rank (per lookup).
+  // rlo == nullptr: the table-wise descriptor above.
+  int world = 0;
+  int rank = 0;
+  const int64_t* rlo = nullptr;
+  const int64_t* roff = nullptr;
 };
 
 // K1 + K5: DLRM dot interaction with the one-hot gather fused in: vector t+1
@@ -351,6 +362,22 @@ hipError_t launch_peer_bag_fp8(const PeerLookupArgs& p, const float* tscale, con
                                int T, int hot, int B, void* out, hipStream_t st);
 hipError_t launch_peer_cache_fill_fp8(const PeerLookupArgs& p, int T, const void* chunk0, const int64_t* keys,
                                       const int32_t* slots, int64_t n, void* rows, int64_t cap, hipStream_t st);
+
+// The peer lookup through the range descriptor (peer_lookup_rows.hip: p.rlo /
+// p.roff / p.world / p.rank set; towner / toff / trows / tremote unused): the
+// six launchers above with each row located by its table's row ranges.
+// tscale != nullptr: fp8 stores (chunk0 as above), else bf16 stores.
+hipError_t launch_dot_interaction_gather_peer_rows(const void* dense, int64_t ldd, const PeerLookupArgs& p,
+                                                   const float* tscale, const void* chunk0, const void* ids,
+                                                   bool ids64, int64_t ldi, int T, int B, void* out, int64_t ldo,
+                                                   int out_cols, hipStream_t st, const void* arena = nullptr,
+                                                   int id_col0 = 0);
+hipError_t launch_peer_bag_rows(const PeerLookupArgs& p, const float* tscale, const void* chunk0, const void* ids,
+                                bool ids64, int64_t ldi, const float* wts, int64_t ldw, const void* arena, int col0,
+                                int T, int hot, int B, void* out, hipStream_t st);
+hipError_t launch_peer_cache_fill_rows(const PeerLookupArgs& p, int T, bool fp8, const void* chunk0,
+                                       const int64_t* keys, const int32_t* slots, int64_t n, void* rows, int64_t cap,
+                                       hipStream_t st);
 
 // K4 (small) for the DLRM bottom MLP: relu(relu(relu(pad64(bf16(wts[:, :nd]))
 // W1^T + b1) W2^T + b2) W3^T + b3) in one kernel (W1 [N1][64], W2 [N2][N1], W3

@@ -90,6 +90,62 @@ __device__ __forceinline__ const bf16* peer_row(const PeerLookupArgs& p, const C
   return reinterpret_cast<const bf16*>(peer_row_bytes<kRowBytesBf16>(p, c, t, v, hit));
 }
 
+// ---- the range descriptor (row-wise and mixed plans, peer_lookup_rows.hip)
+// With p.rlo set a table is cut into `world` contiguous row ranges, rank r
+// holding rows [rlo[t][r], rlo[t][r + 1]) of table t from row roff[t][r] of
+// its store on; a table placed whole is the degenerate case (its owner's
+// range is everything, the others are empty). The rank of row v is the number
+// of inner boundaries at or below v: world - 1 compares with a wave-uniform
+// trip count and no division, and with non-decreasing starts that rank's range
+// is never empty (equal starts - empty ranges - are all counted, so the last
+// of them wins). The (world + 1) x 8 bytes of a table's starts stay in cache.
+__device__ __forceinline__ int64_t range_table_rows(const PeerLookupArgs& p, int t) {
+  return p.rlo[int64_t(t) * (p.world + 1) + p.world];
+}
+
+template <int ROWB>
+__device__ __forceinline__ const uint8_t* range_row_bytes(const PeerLookupArgs& p, int t, int64_t v, int& owner) {
+  const int64_t* lo = p.rlo + int64_t(t) * (p.world + 1);
+  int r = 0;
+  for (int k = 1; k < p.world; ++k) r += v >= lo[k] ? 1 : 0;
+  owner = r;
+  const int64_t g = p.roff[int64_t(t) * p.world + r] + (v - lo[r]);
+  const int64_t c = int64_t(r) * p.max_chunks + (g >> p.chunk_shift);
+  return reinterpret_cast<const uint8_t*>(p.cbase[c]) + (g & ((int64_t(1) << p.chunk_shift) - 1)) * ROWB;
+}
+
+// peer_row_bytes with the range locator: remote is per lookup (owner != rank),
+// the replica cache's keys and probing are the table-wise ones
+template <int ROWB>
+__device__ __forceinline__ const uint8_t* range_peer_row_bytes(const PeerLookupArgs& p, const CacheView& c, int t,
+                                                               int64_t v, int& hit) {
+  int owner;
+  const uint8_t* src = range_row_bytes<ROWB>(p, t, v, owner);
+  hit = -1;
+  if (owner != p.rank) {
+    hit = 0;
+    if (c.mask) {
+      const int64_t key = (int64_t(t) << 40) | v;
+      uint64_t h = cache_hash(key, c.mask);
+      for (int probe = 0; probe < kCacheMaxProbe; ++probe) {
+        const i64x2 e = *reinterpret_cast<const i64x2*>(c.entries + 2 * h);
+        const int64_t k = e[0];
+        if (k == key) {
+          const int64_t s = e[1];
+          if (s >= 0 && s < c.cap) {
+            src = c.rows + s * ROWB;
+            hit = 1;
+          }
+          break;
+        }
+        if (k == kCacheEmpty) break;
+        h = (h + 1) & c.mask;
+      }
+    }
+  }
+  return src;
+}
+
 // Candidates whose remote keys are sampled for the hot set (b % sample_every
 // == 0) and, disjoint from them, candidates whose lookups are counted (b %
 // sample_every == sample_every / 2): a repeating request stream then cannot

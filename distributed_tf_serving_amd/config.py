@@ -55,6 +55,12 @@ class ModelConfig:
     # parallel/hot_cache.py) or
     # "auto" (peer on GPUs that can all load from each other, else alltoall)
     embedding_exchange: str = "auto"
+    # how the planner places the sharded dlrm tables (parallel/embedding_sharding.py plan_sharding):
+    # "table" (each table whole on one rank), "row" (each table cut into one row range per rank: a
+    # table larger than a rank's budget, or a table count that does not divide over the ranks) or
+    # "auto" (behind the peer exchange and for multi-hot tables: "table"). "row" with multi-hot or
+    # fp8 tables needs embedding_exchange: peer (csrc/kernels/peer_lookup_rows.hip)
+    embedding_sharding: str = "auto"
     hot_cache_rows: int = -1
     param_dtype: str = "bf16"         # storage dtype of embeddings + dense weights
     gemm_dtype: str = "bf16"          # bf16 | fp8 (dcn_v2 towers on CDNA4 fp8 MFMA)

@@ -621,14 +621,18 @@ def dot_interaction_gather_peer(dense: torch.Tensor, ids, peer, cache=None, out_
     store over xGMI, or this rank's replica cache of hot remote rows. ``ids``:
     int32/int64 [B, >= id_col0 + T] rows or :class:`ArenaRows`. fp8 peer
     tables (e4m3 code stores + per-table scales) take the fp8 kernel; the
-    output is bf16 either way."""
+    output is bf16 either way. A row-wise descriptor (``peer.row_wise``: each
+    table cut into per-rank row ranges) takes the kernels of
+    peer_lookup_rows.hip, which locate every row's rank first."""
     T = peer.T
     if out_cols <= 0:
         out_cols = interaction_cols(T, dense.shape[1])
     kw = cache.kernel_args() if cache is not None else {}
     if dense.is_cuda:
         fn = hip().dot_interaction_gather_peer
-        if peer.fp8:
+        if peer.row_wise:  # one binding for both store dtypes (peer_lookup_rows.hip)
+            fn, kw = hip().dot_interaction_gather_peer_rows, dict(kw, **(dict(store=peer.mine) if peer.fp8 else {}))
+        elif peer.fp8:
             fn, kw = hip().dot_interaction_gather_peer_fp8, dict(kw, store=peer.mine)
         if isinstance(ids, ArenaRows):
             return fn(dense, None, ids.arena, int(id_col0), out_cols=int(out_cols), **peer.kernel_args(), **kw)
@@ -653,7 +657,9 @@ def peer_bag(ids, wts: Optional[torch.Tensor], B: int, col0: int, hot: int, peer
     kw = cache.kernel_args() if cache is not None else {}
     if dev.type == "cuda":
         fn = hip().peer_bag
-        if peer.fp8:
+        if peer.row_wise:
+            fn, kw = hip().peer_bag_rows, dict(kw, **(dict(store=peer.mine) if peer.fp8 else {}))
+        elif peer.fp8:
             fn, kw = hip().peer_bag_fp8, dict(kw, store=peer.mine)
         if isinstance(ids, ArenaRows):
             fn(None, None, ids.arena, int(B), int(col0), int(hot), out=out, **peer.kernel_args(), **kw)

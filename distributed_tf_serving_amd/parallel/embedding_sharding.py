@@ -21,11 +21,17 @@ parallelism (collective C3):
     rank owns each row, so the bf16 sum is exact.
   Every message has a fixed shape for a given batch size (no count exchange),
   so the step stays HIP-graph capturable on RCCL.
-  - peer (``ModelConfig.embedding_exchange = "peer"``, table-wise): no
-    exchange at all - each rank maps its peers' stores (IPC) and the lookup
-    loads every row where it lives over xGMI, hot remote rows from a per-rank
-    replica cache refreshed from online counts (parallel/hot_cache.py); the
-    bytes crossing xGMI are the cache misses x 128. ``table_dtype: fp8``
+  - peer (``ModelConfig.embedding_exchange = "peer"``; table-wise, row-wise
+    or mixed plans, one-hot or multi-hot): no exchange at all - each rank
+    maps its peers' stores (IPC) and the lookup loads every row where it
+    lives over xGMI, hot remote rows from a per-rank replica cache refreshed
+    from online counts (parallel/hot_cache.py); the bytes crossing xGMI are
+    the cache misses x 128. A table split by rows (``embedding_sharding:
+    row``, or a plan with row-wise placements) needs nothing masked or
+    reduced here: each lane finds the rank whose row range holds its row and
+    reads it there (csrc/kernels/peer_lookup_rows.hip), so a table larger
+    than one rank's budget is served, and a bag's ids may live on different
+    ranks. ``table_dtype: fp8``
     (this exchange only, > 1 rank): the stores are 64-byte rows of e4m3 codes
     with one power-of-two scale per table held on every rank - half the
     shard, misses x 64, and a cached row costs 160 bytes in place of 224.
@@ -204,17 +210,17 @@ class ShardedEmbedding(nn.Module):
         # fp8: the store chunks are e4m3 codes, scale [T] their tables' scales;
         # only the peer lookup reads them (the all-to-all ships bf16 rows)
         self.table_fp8 = table_dtype == "fp8"
-        if self.table_fp8 and (exchange != "peer" or plan.row_wise()):
-            raise ValueError("fp8 tables shard table-wise behind the peer exchange only (exchange='peer', "
-                             "policy='table')")
+        if self.table_fp8 and exchange != "peer":
+            raise ValueError("fp8 tables shard behind the peer exchange only (exchange='peer')")
         self.out_dtype = dtype  # looked-up rows and exchange buffers (bf16 also over an fp8 store)
         self.exchange = exchange
         self.col_base = int(col_base)
         # multi-hot: table t's ids are columns col_base + t * hot .. + hot - 1,
         # pooled (weighted sum) on the owner by the K1b bag kernel
         self.hot = int(hot)
-        if self.hot > 1 and plan.row_wise():
-            raise NotImplementedError("multi-hot tables shard table-wise (plan them with policy='table')")
+        if self.hot > 1 and plan.row_wise() and exchange != "peer":
+            raise NotImplementedError("multi-hot tables shard table-wise (plan them with policy='table'), or "
+                                      "row-wise behind the peer exchange (exchange='peer')")
         dev = torch.device(device)
         T = len(plan.tables)
         self.T = T
@@ -243,8 +249,6 @@ class ShardedEmbedding(nn.Module):
         lay = [layout(r) for r in range(self.world)]
         self.rows_local, my_off, self.segments = lay[self.rank]  # segments: (table, global lo, rows, local offset)
         peer = exchange == "peer" and self.world > 1
-        if peer and self.rw:
-            raise ValueError("the peer exchange shards table-wise (plan the tables with policy='table')")
         shm_tag = None
         if peer and dev.type == "cpu":  # peers map this rank's store from a shared-memory file
             import uuid
@@ -294,11 +298,25 @@ class ShardedEmbedding(nn.Module):
             stores = hot_cache.open_peer_stores(mine, group, shm_tag) if peer else [mine]
             if shm_tag is not None:
                 os.unlink(shm_tag)  # every rank has it mapped (open_peer_stores ends in a barrier)
-            owner = [next(r for r in range(self.world) if t in self.tw_by_rank[r]) for t in range(T)]
-            self.peer = hot_cache.PeerTables(stores, owner, [lay[owner[t]][1][t] for t in range(T)],
-                                             [plan.tables[t].rows for t in range(T)], self.rank,
-                                             chunk_shift=hot_cache.CHUNK_SHIFT if peer else None,
-                                             scale=self.emb_scale)
+            trows = [plan.tables[t].rows for t in range(T)]
+            shift = hot_cache.CHUNK_SHIFT if peer else None
+            if self.rw:
+                # row ranges (lo, n, store offset) per table and rank, from every rank's layout; a table
+                # placed whole is the degenerate case: its owner holds [0, rows), the others nothing
+                ranges = []
+                for t in range(T):
+                    if t in self.rw:
+                        ranges.append([(*plan.placement(t).ranges[r], lay[r][1][t]) for r in range(self.world)])
+                    else:
+                        o = plan.placement(t).rank
+                        ranges.append([(0, trows[t], lay[o][1][t]) if r == o else (0 if r < o else trows[t], 0, 0)
+                                       for r in range(self.world)])
+                self.peer = hot_cache.PeerTables(stores, None, None, trows, self.rank, chunk_shift=shift,
+                                                 scale=self.emb_scale, ranges=ranges)
+            else:
+                owner = [next(r for r in range(self.world) if t in self.tw_by_rank[r]) for t in range(T)]
+                self.peer = hot_cache.PeerTables(stores, owner, [lay[owner[t]][1][t] for t in range(T)], trows,
+                                                 self.rank, chunk_shift=shift, scale=self.emb_scale)
             if peer and cache_rows != 0 and self.peer.remote_tables:  # < 0: sized from free HBM
                 self.cache = hot_cache.HotRowCache(self.peer, cache_rows, sample_every=cache_sample_every)
         i64 = dict(dtype=torch.int64, device=dev)
@@ -397,6 +415,8 @@ class ShardedEmbedding(nn.Module):
             return 0
         eb = self.store.element_size()
         if self.peer is not None:
+            if self.peer.row_wise:  # uniformly drawn rows: each table's remote row share of its lookups
+                return int(B * self.T * hot * D * eb * self.peer.remote_row_fraction)
             return B * self.peer.remote_tables * hot * D * eb
         n = 0
         if self.tw_tables:
@@ -526,6 +546,8 @@ def build_parallel_model(cfg: ModelConfig, device, ctx: Optional[DistContext] = 
     from ..models import build_model
 
     ctx = ctx or DistContext(device=torch.device(device))
+    if policy == "auto":  # ModelConfig.embedding_sharding: auto | table | row
+        policy = getattr(cfg, "embedding_sharding", "auto")
     if cfg.family == "dlrm" and (shard_tables == "on" or (shard_tables == "auto" and ctx.is_distributed)):
         _reject_fp8_tables(cfg, ctx.world if ctx.is_distributed else 1)
         return ShardedDLRM(cfg, ctx, device=device, policy=policy, budget_bytes=budget_bytes, group=group).eval()
@@ -555,8 +577,9 @@ class ShardedDLRM(nn.Module):
         if exchange == "auto":
             exchange = "peer" if peer_access_everywhere(ctx, torch.device(device), group) else "alltoall"
         if (self.hot > 1 or exchange == "peer") and policy == "auto":
-            # multi-hot bags pool on their table's owner; peers read whole
-            # tables where they live
+            # multi-hot bags pool on their table's owner; the peer exchange's
+            # default stays whole tables (an explicit "row", or a plan passed
+            # in, is honoured: ModelConfig.embedding_sharding)
             policy = "table"
         self.plan = plan or plan_sharding(dlrm_tables(cfg), world, budget_bytes, policy)
         self.dense = DLRM(cfg, device=device, materialize_tables=False)

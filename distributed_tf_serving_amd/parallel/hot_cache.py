@@ -1,4 +1,4 @@
-"""Peer lookup and the hot-row replica cache for table-wise sharded embeddings.
+"""Peer lookup and the hot-row replica cache for sharded embeddings (table-wise or by row ranges).
 
 SURVEY §2.4 K1b / §2.5 C3 asks for embedding model parallelism over 8 GPUs;
 the reference has no sharded embeddings at all (its TF-Serving shards each run
@@ -68,13 +68,33 @@ class PeerTables:
 
     fp8 tables (``table_dtype: fp8``): every chunk of every rank holds
     ``float8_e4m3fn`` codes and ``scale`` (fp32 [T], powers of two, the same on
-    every rank) gives table t's values as ``float(code) * scale[t]``."""
+    every rank) gives table t's values as ``float(code) * scale[t]``.
 
-    def __init__(self, stores: Sequence, owner: Sequence[int], off: Sequence[int], rows: Sequence[int], rank: int,
-                 chunk_shift: Optional[int] = None, scale: Optional[torch.Tensor] = None):
+    Row-wise and mixed plans (``ranges``, csrc/kernels/peer_lookup_rows.hip):
+    ``ranges[t][r] = (lo, n, off)`` - rank r holds rows ``lo .. lo + n`` of
+    table t from row ``off`` of its store on. The ranges of a table are
+    contiguous pieces in rank order covering ``0 .. rows[t]``; empty ones are
+    legal (a table with fewer rows than ranks, or a table placed whole: its
+    owner's range is everything). ``owner`` / ``off`` are then unused (None),
+    ``row_wise`` is set, a lookup is remote when its row lies outside this
+    rank's range (:meth:`remote_cpu`), and the kernels take the checked
+    descriptor ``ranges_desc`` (``rlo`` [T, W + 1] cumulative starts, ``roff``
+    [T, W] store offsets)."""
+
+    def __init__(self, stores: Sequence, owner: Optional[Sequence[int]], off: Optional[Sequence[int]],
+                 rows: Sequence[int], rank: int, chunk_shift: Optional[int] = None,
+                 scale: Optional[torch.Tensor] = None, ranges: Optional[Sequence[Sequence[Tuple[int, int, int]]]] = None):
         self.stores = [[s] if isinstance(s, torch.Tensor) else list(s) for s in stores]
-        self.owner, self.off, self.rows, self.rank = list(owner), list(off), list(rows), int(rank)
-        self.T = len(self.owner)
+        self.rows, self.rank = list(rows), int(rank)
+        self.row_wise = ranges is not None
+        self.T = len(self.rows)
+        self.world = len(self.stores)
+        if self.row_wise:
+            self.owner = self.off = None
+            self.ranges = [[tuple(int(x) for x in seg) for seg in rr] for rr in ranges]
+        else:
+            self.owner, self.off = list(owner), list(off)
+            self.T = len(self.owner)
         if chunk_shift is None:
             if all(len(c) == 1 for c in self.stores):
                 chunk_shift = max(1, max(int(c[0].shape[0]) for c in self.stores) - 1).bit_length()
@@ -90,10 +110,14 @@ class PeerTables:
                 if c.shape[0] > per or (i < len(chunks) - 1 and c.shape[0] != per):
                     raise ValueError(f"rank {r} chunk {i}: {c.shape[0]} rows, chunks hold 2^{self.chunk_shift}")
             total.append(sum(int(c.shape[0]) for c in chunks))
-        for t in range(self.T):
-            if self.off[t] < 0 or self.off[t] + self.rows[t] > total[self.owner[t]]:
-                raise ValueError(f"table {t}: rows {self.off[t]}..{self.off[t] + self.rows[t]} outside its owner's "
-                                 f"store ({total[self.owner[t]]} rows)")
+        self.store_rows = total
+        if self.row_wise:
+            self._check_ranges(total)
+        else:
+            for t in range(self.T):
+                if self.off[t] < 0 or self.off[t] + self.rows[t] > total[self.owner[t]]:
+                    raise ValueError(f"table {t}: rows {self.off[t]}..{self.off[t] + self.rows[t]} outside its "
+                                     f"owner's store ({total[self.owner[t]]} rows)")
         mine = self.stores[self.rank][0]
         dev = mine.device
         self.dtype = mine.dtype
@@ -116,33 +140,98 @@ class PeerTables:
         maxc = max(len(c) for c in self.stores)
         i64 = dict(dtype=torch.int64, device=dev)
         self.trows = torch.tensor(self.rows, **i64)
+        self.cbase = torch.tensor([[c.data_ptr() for c in chunks] + [0] * (maxc - len(chunks))
+                                   for chunks in self.stores], **i64)
+        self.trows_cpu = torch.tensor(self.rows, dtype=torch.int64)
+        self.ranges_desc = None
+        if self.row_wise:
+            self.rlo_cpu = torch.tensor([[seg[0] for seg in rr] + [self.rows[t]] for t, rr in enumerate(self.ranges)],
+                                        dtype=torch.int64).view(self.T, self.world + 1)
+            self.roff_cpu = torch.tensor([[seg[2] for seg in rr] for rr in self.ranges],
+                                         dtype=torch.int64).view(self.T, self.world)
+            here = self.rlo_cpu[:, self.rank + 1] - self.rlo_cpu[:, self.rank]  # rows of each table on this rank
+            self.tremote_cpu = here < self.trows_cpu  # tables with at least one remote row
+            self.toff = self.towner = self.tremote = None
+            if dev.type == "cuda":
+                from ..ops import hip
+
+                # checked against the stores once more by the bindings; the kernels take only this object
+                self.ranges_desc = hip().peer_row_ranges(self.cbase, self.rlo_cpu, self.roff_cpu, self.trows_cpu,
+                                                         torch.tensor(total, dtype=torch.int64), self.rank,
+                                                         self.chunk_shift)
+                self.rlo, self.roff = self.ranges_desc.rlo, self.ranges_desc.roff
+            else:
+                self.rlo, self.roff = self.rlo_cpu, self.roff_cpu
+            self.remote_rows = int((self.trows_cpu - here).sum())
+            # the share of remote lookups when every table is looked up once per candidate with
+            # uniformly drawn rows: the mean over the tables of each table's remote row share
+            self.remote_row_fraction = float(((self.trows_cpu - here).double() / self.trows_cpu.double()).mean())
+            return
         self.toff = torch.tensor(self.off, **i64)
         self.towner = torch.tensor(self.owner, dtype=torch.int32, device=dev)
         self.tremote = torch.tensor([int(o != self.rank) for o in self.owner], dtype=torch.int32, device=dev)
-        self.cbase = torch.tensor([[c.data_ptr() for c in chunks] + [0] * (maxc - len(chunks))
-                                   for chunks in self.stores], **i64)
         self._owner_cpu = torch.tensor(self.owner, dtype=torch.int64)
         self._off_cpu = torch.tensor(self.off, dtype=torch.int64)
-        self.trows_cpu = torch.tensor(self.rows, dtype=torch.int64)
         self.tremote_cpu = self.tremote.cpu().bool()
+        self.remote_rows = int(sum(int(r) for r, rem in zip(self.rows, self.tremote_cpu.tolist()) if rem))
+        self.remote_row_fraction = self.remote_tables / max(1, self.T)
+
+    def _check_ranges(self, total: List[int]) -> None:
+        if len(self.ranges) != self.T:
+            raise ValueError(f"ranges for {len(self.ranges)} tables, rows for {self.T}")
+        for t, rr in enumerate(self.ranges):
+            if len(rr) != self.world or any(len(seg) != 3 for seg in rr):
+                raise ValueError(f"table {t}: one (lo, n, off) range per rank ({self.world}), got {rr}")
+            if self.rows[t] < 1:
+                raise ValueError(f"table {t}: {self.rows[t]} rows")
+            at = 0
+            for r, (lo, n, off) in enumerate(rr):
+                if n < 0 or lo < at:
+                    raise ValueError(f"table {t}: rank {r}'s range starts at {lo} with {n} rows: the starts must not "
+                                     f"decrease (rank {r - 1}'s range ends at {at})")
+                if lo != at:
+                    raise ValueError(f"table {t}: a gap - rank {r}'s range starts at {lo}, rank {r - 1}'s ends at {at}")
+                if off < 0 or off + n > total[r]:
+                    raise ValueError(f"table {t}: rank {r}'s rows {off}..{off + n} outside its store ({total[r]} rows)")
+                at = lo + n
+            if at != self.rows[t]:
+                raise ValueError(f"table {t}: the ranges cover {at} rows, the table has {self.rows[t]}")
 
     def kernel_args(self) -> dict:
-        kw = dict(cbase=self.cbase, towner=self.towner, toff=self.toff, trows=self.trows, tremote=self.tremote,
-                  chunk_shift=self.chunk_shift)
+        if self.row_wise:  # the bindings of peer_lookup_rows.hip: rlo / roff / world / rank inside the checked descriptor
+            kw = dict(desc=self.ranges_desc)
+        else:
+            kw = dict(cbase=self.cbase, towner=self.towner, toff=self.toff, trows=self.trows, tremote=self.tremote,
+                      chunk_shift=self.chunk_shift)
         if self.fp8:
             kw["tscale"] = self.scale
         return kw
 
     @property
     def remote_tables(self) -> int:
+        """Tables owned by another rank; row-wise: tables with at least one remote row."""
         return int(self.tremote_cpu.sum())
+
+    def locate_cpu(self, t: torch.Tensor, v: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(rank, store row) holding rows v of tables t (int64 [n] each)."""
+        if not self.row_wise:
+            return self._owner_cpu[t], self._off_cpu[t] + v
+        lo = self.rlo_cpu[t]  # the kernels' locator: the number of inner boundaries at or below v
+        own = (v.unsqueeze(1) >= lo[:, 1:self.world]).sum(1)
+        return own, self.roff_cpu[t, own] + (v - lo.gather(1, own.unsqueeze(1)).squeeze(1))
+
+    def remote_cpu(self, t: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+        """Bool [n]: row v of table t lives on another rank (per lookup on a
+        row-wise descriptor, per table otherwise)."""
+        if not self.row_wise:
+            return self.tremote_cpu[t]
+        return self.locate_cpu(t, v)[0] != self.rank
 
     def row_cpu(self, t: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
         """Rows v of tables t (int64 [n] each) read from their owners' stores
         (raw rows in the store dtype: codes for fp8 tables)."""
         out = torch.empty(t.numel(), D, dtype=self.dtype)
-        own = self._owner_cpu[t]
-        g = self._off_cpu[t] + v
+        own, g = self.locate_cpu(t, v)
         chunk = g >> self.chunk_shift
         local = g & ((1 << self.chunk_shift) - 1)
         key = own * (1 << 20) + chunk
@@ -178,7 +267,10 @@ def auto_capacity(peer: "PeerTables", free_bytes: Optional[int] = None, fraction
     cache. MI355X: ~250 GB free beside a 2 x 38 GB sharded DLRM -> room for
     every remote row of the round-4 rehearsal tables; the cap keeps small
     models from reserving memory they cannot use."""
-    remote_rows = int(sum(int(r) for r, rem in zip(peer.rows, peer.tremote_cpu.tolist()) if rem))
+    if peer.row_wise:  # the rows outside this rank's ranges
+        remote_rows = peer.remote_rows
+    else:
+        remote_rows = int(sum(int(r) for r, rem in zip(peer.rows, peer.tremote_cpu.tolist()) if rem))
     if remote_rows == 0:
         return 0
     if free_bytes is None:
@@ -207,7 +299,12 @@ class HotRowCache:
     owners' e4m3 code bytes verbatim for fp8 tables) behind two open-addressing index
     buffers ({key, slot} int64 entries [H, 2], H = the power of two >= 2 x
     capacity; one 16-byte load per probe): one serves the steps while
-    :meth:`refresh` rebuilds the other.
+    :meth:`refresh` rebuilds the other. The kernels probe at most 32 entries
+    and the hash takes bits 24.. of key x an odd constant, so the table number
+    (key bits 40..) separates tables only in an index of 2^17 entries or more
+    (all 31 from 2^21): a small cache whose tables share their hot row numbers
+    chains the same row of every table on one slot, and rows past the 32nd
+    probe are cached but served from their owners (counted as misses).
     ``desc`` (int64 [5], read by the kernels at their start) = {active index,
     sample period, H - 1, rows, capacity}: a refresh changes only its first
     word (one 8-byte store), so a kernel sees the old index or the new one,
@@ -435,7 +532,10 @@ class HotRowCache:
         if self.device.type == "cuda":
             from ..ops import hip
 
-            if p.fp8:
+            if p.row_wise:
+                hip().peer_cache_fill_rows(keys, slots, rows=self.rows, **p.kernel_args(),
+                                           **(dict(store=p.mine) if p.fp8 else {}))
+            elif p.fp8:
                 hip().peer_cache_fill_fp8(keys, slots, rows=self.rows, store=p.mine, **p.kernel_args())
             else:
                 hip().peer_cache_fill(keys, slots, rows=self.rows, **p.kernel_args())
@@ -501,7 +601,7 @@ def peer_gather_cpu(peer: PeerTables, cache: Optional[HotRowCache], ids: torch.T
     v = torch.remainder(ids.long().reshape(-1), peer.trows_cpu[t])
     rows = peer.values_cpu(peer.row_cpu(t, v), t)
     if cache is not None:
-        remote = peer.tremote_cpu[t]
+        remote = peer.remote_cpu(t, v)
         keys = (t << KEY_SHIFT) | v
         slot = cache.lookup_cpu(keys)
         hit = remote & (slot >= 0)

@@ -10,6 +10,10 @@ On one GPU the "remote" store is local HBM, so this measures the lookup's own
 overhead (chunk addressing, cache probes, counters, sampling), not xGMI.
 ``--table-dtype fp8``: the same three on e4m3 code stores with per-table
 scales (``local`` is then ``dot_interaction_gather_fp8``).
+``--policy row``: the same logical tables cut into one row range per store
+(``--ranks`` stores on this GPU, rank 0's view) and read through the row-wise
+kernels (csrc/kernels/peer_lookup_rows.hip) - against a ``--policy table`` run
+of the same arguments this times the row locator.
 Prints one JSON line."""
 from __future__ import annotations
 
@@ -28,6 +32,8 @@ def main() -> None:
     ap.add_argument("--cache-rows", type=int, default=1 << 20)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--table-dtype", choices=("bf16", "fp8"), default="bf16")
+    ap.add_argument("--policy", choices=("table", "row"), default="table")
+    ap.add_argument("--ranks", type=int, default=2, help="--policy row: stores the tables are cut over")
     a = ap.parse_args()
     from distributed_tf_serving_amd import ops
     from distributed_tf_serving_amd.client.synth import SyntheticRequests
@@ -50,12 +56,23 @@ def main() -> None:
         else:
             x.uniform_(-0.05, 0.05)
 
-    stores = [alloc_store(n0, sdt, dev), alloc_store(n1, sdt, dev)]
+    row = a.policy == "row"
+    if row:
+        from distributed_tf_serving_amd.parallel.dist import split_rows
+
+        pieces = split_rows(R, a.ranks)  # store r holds rows [lo, lo + n) of every table, table after table
+        stores = [alloc_store(T * n, sdt, dev) for _, n in pieces]
+    else:
+        stores = [alloc_store(n0, sdt, dev), alloc_store(n1, sdt, dev)]
     for chunks in stores:
         for c in chunks:
             fill(c)
-    off = [t * R if t < half else (t - half) * R for t in range(T)]
-    peer = PeerTables(stores, own, off, [R] * T, rank=0, chunk_shift=CHUNK_SHIFT, scale=scale)
+    if row:
+        peer = PeerTables(stores, None, None, [R] * T, rank=0, chunk_shift=CHUNK_SHIFT, scale=scale,
+                          ranges=[[(lo, n, t * n) for lo, n in pieces] for t in range(T)])
+    else:
+        off = [t * R if t < half else (t - half) * R for t in range(T)]
+        peer = PeerTables(stores, own, off, [R] * T, rank=0, chunk_shift=CHUNK_SHIFT, scale=scale)
     # the local form: every table in one [T x R, 64] store (separate buffer, same values not needed)
     local = torch.empty(T * R, 64, dtype=sdt, device=dev)
     fill(local)
@@ -78,6 +95,9 @@ def main() -> None:
         return e0.elapsed_time(e1) * 1e3 / a.iters
 
     out = {"table_dtype": a.table_dtype, "batch": B, "tables": T, "rows_per_table": R, "remote_tables": T - half}
+    if row:
+        out.update(policy="row", ranks=a.ranks, remote_tables=peer.remote_tables,
+                   remote_row_fraction=round(peer.remote_row_fraction, 4))
     if fp8:
         out["local_us"] = round(timed(lambda ids: ops.dot_interaction_gather_fp8(dense, local, scale, ids, modf, offf)), 2)
     else:
@@ -96,7 +116,9 @@ def main() -> None:
     # the same lookups without the counters / sampling, and the counters alone
     raw = hip().dot_interaction_gather_peer
     pk = peer.kernel_args()
-    if fp8:
+    if row:
+        raw, pk = hip().dot_interaction_gather_peer_rows, dict(pk, **(dict(store=peer.mine) if fp8 else {}))
+    elif fp8:
         raw, pk = hip().dot_interaction_gather_peer_fp8, dict(pk, store=peer.mine)
     out["peer_cache_no_counters_us"] = round(timed(lambda ids: raw(dense, ids, None, 0, cache=cache.desc, **pk)), 2)
     out["peer_counters_only_us"] = round(timed(lambda ids: raw(
@@ -108,8 +130,10 @@ def main() -> None:
     fresh = synth.arrays(B)[0].astype(np.int64) % R
     keys = cache.keys.cpu().numpy()
     hit = tot = 0
-    for t in range(half, T):
+    for t in range(0 if row else half, T):
         k = (np.int64(t) << 40) | fresh[:, t]
+        if row:
+            k = k[fresh[:, t] >= pieces[0][1]]  # the rows outside rank 0's range
         pos = np.clip(np.searchsorted(keys, k), 0, max(0, keys.size - 1))
         hit += int((keys[pos] == k).sum()) if keys.size else 0
         tot += k.size

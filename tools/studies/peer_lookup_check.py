@@ -6,6 +6,8 @@ interaction kernel) and multi-hot bags - before and after the hot-row replica
 cache fills, through the eager forward and through the arena step program.
 ``--table-dtype fp8``: both models hold fp8 tables (e4m3 code stores behind
 the peer lookup against the unsharded fp8 DLRM of the same seed).
+``--policy row``: every table is cut into one row range per rank and read
+through the row-wise peer kernels (csrc/kernels/peer_lookup_rows.hip).
 Rank 0 prints one JSON line."""
 from __future__ import annotations
 
@@ -23,6 +25,7 @@ def main() -> int:
     ap.add_argument("--batch", type=int, default=2048)
     ap.add_argument("--hot", type=int, default=1)
     ap.add_argument("--table-dtype", choices=("bf16", "fp8"), default="bf16")
+    ap.add_argument("--policy", choices=("table", "row"), default="table")
     a = ap.parse_args()
     from distributed_tf_serving_amd import ops
     from distributed_tf_serving_amd.client.synth import SyntheticRequests
@@ -43,13 +46,16 @@ def main() -> int:
     cfg = ModelConfig(family="dlrm", num_fields=13 + T * a.hot, num_dense=13, table_rows=a.rows, embed_dim=64,
                       multi_hot=a.hot, embedding_exchange="peer", hot_cache_rows=4096,
                       table_dtype=a.table_dtype)
-    m = ShardedDLRM(cfg, ctx, device=dev)
+    m = ShardedDLRM(cfg, ctx, device=dev, policy="row" if a.policy == "row" else "auto")
     ref = build_model(cfg, dev)  # the unsharded DLRM, same seed
     cache = m.cache
     assert cache is not None and not m.has_collectives
     cache.sample_every = 1
     synth = SyntheticRequests(fields=cfg.num_fields, id_space=1 << 40, dist="zipf", seed=17 + ctx.rank)
     res = {"world": ctx.world, "hot": a.hot, "table_dtype": a.table_dtype, "remote_tables": m.emb.peer.remote_tables, "rounds": []}
+    if a.policy == "row":
+        assert m.emb.peer.row_wise and len(m.emb.rw) == T
+        res["policy"] = "row"
     F = cfg.num_fields
     for rnd in range(3):
         ids_np, wts_np = synth.arrays(a.batch)
