@@ -2211,7 +2211,12 @@ uint64_t scatter_step(dtfs::runtime::StepRunner& r, dtfs::runtime::SharedScatter
   int ai = -1;
   if (!sc.wait_plan(k, timeout_us, &mine, &ai))
     throw std::runtime_error("shared scatter: no plan for step " + std::to_string(k) + " from rank 0");
-  const auto copies = dtfs::runtime::share_copies(sc.arena(ai), mine, sc.stage(slot));
+  // the share's bytes go through the slot's pinned staging arena (the device
+  // cannot read the segment), once the slot's previous copy has left it
+  r.wait_h2d(slot);
+  uint8_t* staging = sc.staging(slot);
+  auto copies = dtfs::runtime::share_copies(sc.arena(ai), mine, staging);
+  dtfs::runtime::stage_copies(copies, staging, sc.arena_cap());
   int64_t n = 0;
   for (const auto& c : copies) {
     if (c.dst_off < 0 || c.dst_off + c.n > dst_cap) throw std::runtime_error("shared scatter: share outside the device arena");
@@ -2226,6 +2231,7 @@ uint64_t scatter_step(dtfs::runtime::StepRunner& r, dtfs::runtime::SharedScatter
 bool scatter_wait(dtfs::runtime::StepRunner& r, dtfs::runtime::SharedScatter& sc, int slot, uint64_t k,
                   int64_t timeout_us, const std::vector<dtfs::comm::RcclComm*>& comms, std::string* err) {
   if (!r.wait_for(slot, timeout_us, comms, err)) return false;
+  sc.publish_scores(k, slot);
   sc.mark_done(k);
   if (sc.rank() != 0) return true;
   if (!sc.wait_done(k, timeout_us, err)) return false;
@@ -2346,7 +2352,8 @@ PyGpuLive* make_gpu_live(py::object runner_obj, py::dict cfg, py::list buckets, 
     for (auto d : t[1].cast<py::list>()) v.push_back(loop_slot_from(d.cast<py::dict>(), &p->keep));
     slots.push_back(std::move(v));
   }
-  auto ar = dtfs_live::arenas_from(arenas, true, &p->keep);
+  // shared scatter: rank 0 batches into the segment's arenas, and every share is staged in pinned memory
+  auto ar = dtfs_live::arenas_from(arenas, scatter.is_none(), &p->keep);
   p->backend = std::make_unique<GpuBackend>(&runner, std::move(rows), std::move(slots));
   if (auto* sc = dtfs_live::scatter_from(scatter, &p->keep)) {
     const auto lc = dtfs_live::live_config_from(cfg);
@@ -2643,12 +2650,14 @@ PYBIND11_MODULE(_hip, m) {
   {
     auto sc = dtfs_live::def_shared_scatter(m);
     sc.def(
-          "register_with_gpu",
+          "pin_for_gpu",
           [](dtfs::runtime::SharedScatter& s) {
-            // every rank pins the whole mapping for its own GPU: its DMA reads
-            // rank 0's arenas, its head kernel writes the shared scores
-            check_hip(hipHostRegister(s.base(), s.bytes(), hipHostRegisterMapped), "hipHostRegister(shared scatter)");
-            s.set_on_unmap([](void* p, size_t) { (void)hipHostUnregister(p); });
+            // every rank's own pinned block: its DMA reads its share of rank
+            // 0's arenas from there, its head kernel writes its scores there
+            void* p = nullptr;
+            check_hip(hipHostMalloc(&p, s.pinned_bytes(), hipHostMallocNumaUser), "hipHostMalloc(shared scatter)");
+            std::memset(p, 0, s.pinned_bytes());
+            s.set_pinned(p, [](void* q) { (void)hipHostFree(q); });
           })
         .def(
             "launch",
@@ -2682,22 +2691,22 @@ PYBIND11_MODULE(_hip, m) {
   }
 
   m.def("rccl_set_library", &dtfs::comm::set_library, py::arg("path"));
-  // NUMA-local pinned host memory (runtime/numa.h): pages placed on `node`
-  // first, then registered with the GPU; freed by unregister + munmap
+  // NUMA-local pinned host memory (runtime/numa.h): allocated pinned while the
+  // calling thread's memory policy binds it to `node` (hipHostMallocNumaUser
+  // follows that policy), touched, then the thread's policy is put back
   m.def(
       "alloc_pinned_on_node",
       [](int64_t bytes, int node) {
-        void* p = dtfs::runtime::alloc_on_node(size_t(bytes), node);
-        if (hipHostRegister(p, size_t(bytes), hipHostRegisterDefault) != hipSuccess) {
-          dtfs::runtime::free_on_node(p, size_t(bytes));
-          throw std::runtime_error("hipHostRegister failed");
+        TORCH_CHECK(bytes > 0, "alloc_pinned_on_node: bytes must be positive");
+        void* p = nullptr;
+        hipError_t e;
+        {
+          dtfs::runtime::ScopedNodeBind bind(node);
+          e = hipHostMalloc(&p, size_t(bytes), hipHostMallocNumaUser);
+          if (e == hipSuccess) std::memset(p, 0, size_t(bytes));
         }
-        const size_t n = size_t(bytes);
-        return torch::from_blob(p, {bytes},
-                                [n](void* q) {
-                                  (void)hipHostUnregister(q);
-                                  dtfs::runtime::free_on_node(q, n);
-                                },
+        check_hip(e, "hipHostMalloc(node-local arena)");
+        return torch::from_blob(p, {bytes}, [](void* q) { (void)hipHostFree(q); },
                                 torch::TensorOptions().dtype(torch::kUInt8));
       },
       py::arg("bytes"), py::arg("node"));

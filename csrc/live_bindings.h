@@ -97,8 +97,8 @@ inline void def_step_control(py::module& m) {
 }
 
 // SharedScatter (runtime/shared_scatter.h) of this module (module-local like
-// StepControl). Host-side operations only; the GPU module adds registration
-// and the device launch (bindings_hip.cpp).
+// StepControl). Host-side operations only; the GPU module adds the pinned
+// block and the device launch (bindings_hip.cpp).
 using dtfs::runtime::SharedScatter;
 using ScatterClass = py::class_<SharedScatter, std::shared_ptr<SharedScatter>>;
 
@@ -146,7 +146,8 @@ inline ScatterClass def_shared_scatter(py::module& m) {
       .def(
           "out",
           [](SharedScatter& s, int slot) {
-            return torch::from_blob(s.out(slot), {s.out_floats()}, torch::TensorOptions().dtype(torch::kFloat32));
+            // a GPU rank's pinned output (where its step writes), else the shared one
+            return torch::from_blob(s.step_out(slot), {s.out_floats()}, torch::TensorOptions().dtype(torch::kFloat32));
           },
           py::arg("slot"))
       .def(

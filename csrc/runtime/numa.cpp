@@ -101,6 +101,19 @@ bool prefer_numa_node(int node) {
   return syscall(SYS_set_mempolicy, kMpolPreferred, m.bits, (unsigned long)kMaxNodes) == 0;
 }
 
+ScopedNodeBind::ScopedNodeBind(int node) {
+  static_assert(sizeof(saved_mask_) == kMaxNodes / 8, "saved_mask_ holds kMaxNodes bits");
+  if (node < 0 || node >= kMaxNodes) return;
+  // best effort like alloc_on_node: without NUMA support the policy stays as it is
+  if (syscall(SYS_get_mempolicy, &saved_mode_, saved_mask_, (unsigned long)kMaxNodes, nullptr, 0ul) != 0) return;
+  NodeMask m(node);
+  bound_ = syscall(SYS_set_mempolicy, kMpolBind, m.bits, (unsigned long)kMaxNodes) == 0;
+}
+
+ScopedNodeBind::~ScopedNodeBind() {
+  if (bound_) syscall(SYS_set_mempolicy, saved_mode_, saved_mask_, (unsigned long)kMaxNodes);
+}
+
 void* alloc_on_node(size_t bytes, int node) {
   const size_t pg = size_t(sysconf(_SC_PAGESIZE));
   bytes = (bytes + pg - 1) / pg * pg;

@@ -6,10 +6,9 @@
 // copy - and the H2D copy is most of the DeepFM step period. So each rank
 // finds its GPU's NUMA node from the PCI bus id (sysfs), pins its threads to
 // that node's CPUs (sched_setaffinity for every thread of the process, new
-// threads inherit) and allocates its arenas on that node (mmap + mbind +
-// first touch) before registering them with the GPU (hipHostRegister, in the
-// _hip module). The reference has no host placement at all (a Java client
-// against remote hosts, DCNClient.java:118-125).
+// threads inherit) and allocates its arenas pinned on that node (hipHostMalloc
+// under ScopedNodeBind, in the _hip module). The reference has no host
+// placement at all (a Java client against remote hosts, DCNClient.java:118-125).
 #pragma once
 
 #include <cstddef>
@@ -27,6 +26,23 @@ int pci_numa_node(const std::string& bus_id);           // "0000:65:00.0" -> nod
 int bind_process_cpus(const std::vector<int>& cpus);
 // This thread's future allocations prefer `node` (set_mempolicy MPOL_PREFERRED).
 bool prefer_numa_node(int node);
+// While it lives, this thread's allocations are bound to `node` (set_mempolicy
+// MPOL_BIND); then the thread's earlier policy is put back. For memory that
+// an allocator of its own places, such as pinned memory from the HIP runtime.
+// No-op for node < 0 or without NUMA support.
+class ScopedNodeBind {
+ public:
+  explicit ScopedNodeBind(int node);
+  ~ScopedNodeBind();
+  ScopedNodeBind(const ScopedNodeBind&) = delete;
+  ScopedNodeBind& operator=(const ScopedNodeBind&) = delete;
+  bool bound() const { return bound_; }
+
+ private:
+  bool bound_ = false;
+  int saved_mode_ = 0;
+  unsigned long saved_mask_[1024 / (8 * sizeof(unsigned long))] = {};
+};
 // Anonymous memory whose pages live on `node` (mbind MPOL_BIND, touched).
 // Page-aligned; free with free_on_node(p, bytes).
 void* alloc_on_node(size_t bytes, int node);

@@ -133,6 +133,16 @@ std::vector<ShareCopy> share_copies(const uint8_t* arena, const RankShare& s, ui
   return c;
 }
 
+void stage_copies(std::vector<ShareCopy>& copies, uint8_t* staging, int64_t cap) {
+  for (ShareCopy& c : copies) {
+    if (c.n <= 0) continue;
+    if (c.dst_off < 0 || c.dst_off + c.n > cap) throw std::out_of_range("shared scatter: share outside the staging arena");
+    uint8_t* at = staging + c.dst_off;
+    if (c.src != at) std::memmove(at, c.src, size_t(c.n));
+    c.src = at;
+  }
+}
+
 std::vector<NodeSlice> scatter_placement(int64_t arenas_off, int n_arenas, int64_t arena_stride, int64_t payload_off,
                                          int64_t expected_payload, const std::vector<int>& rank_nodes) {
   std::vector<NodeSlice> out;
@@ -235,13 +245,31 @@ SharedScatter::SharedScatter(const std::string& name, int world, int rank, bool 
 
 SharedScatter::~SharedScatter() {
   if (!base_) return;
-  if (on_unmap_) on_unmap_(base_, bytes_);
+  if (pinned_ && release_pinned_) release_pinned_(pinned_);
   munmap(base_, bytes_);
 }
 
-uint8_t* SharedScatter::stage(int slot) const {
-  if (slot < 0 || slot >= kScatterMaxSlots) throw std::out_of_range("shared scatter: slot beyond the header stages");
-  return s_->stage[rank_][slot];
+size_t SharedScatter::pinned_bytes() const {
+  return size_t(s_->slots) * size_t(page_up(s_->arena_cap) + page_up(s_->out_floats * 4));
+}
+
+void SharedScatter::set_pinned(void* p, std::function<void(void*)> release) {
+  if (pinned_) throw std::logic_error("shared scatter: pinned block already set");
+  pinned_ = static_cast<uint8_t*>(p);
+  release_pinned_ = std::move(release);
+}
+
+uint8_t* SharedScatter::staging(int slot) const {
+  if (slot < 0 || slot >= s_->slots) throw std::out_of_range("shared scatter: slot");
+  if (!pinned_) throw std::logic_error("shared scatter: no pinned block");
+  return pinned_ + int64_t(slot) * page_up(s_->arena_cap);
+}
+
+float* SharedScatter::step_out(int slot) const {
+  if (!pinned_) return out(slot);
+  if (slot < 0 || slot >= s_->slots) throw std::out_of_range("shared scatter: slot");
+  return reinterpret_cast<float*>(pinned_ + int64_t(s_->slots) * page_up(s_->arena_cap) +
+                                  int64_t(slot) * page_up(s_->out_floats * 4));
 }
 
 uint8_t* SharedScatter::arena(int i) const {
@@ -301,15 +329,27 @@ void SharedScatter::compact_scores(uint64_t k, int slot) {
   // its first row (ascending ranks: destinations never pass their sources)
   const StepPlan& P = s_->plans[k % kPlanRing];
   if (P.seq.load(std::memory_order_acquire) != k + 1) throw std::logic_error("shared scatter: plan overwritten");
-  float* o = out(slot);
+  float* o = step_out(slot);
+  const float* from = out(slot);  // where ranks > 0 left their scores
   for (int r = 1; r < P.world; ++r) {
     const RankShare& sh = P.share[r];
     const int64_t src = int64_t(r) * P.rows_per_rank;
-    if (sh.rows > 0 && sh.row0 != src) {
+    if (sh.rows > 0 && (sh.row0 != src || from != o)) {
       if (src + sh.rows > s_->out_floats) throw std::out_of_range("shared scatter: share outside the output");
-      std::memmove(o + sh.row0, o + src, size_t(sh.rows) * sizeof(float));
+      std::memmove(o + sh.row0, from + src, size_t(sh.rows) * sizeof(float));
     }
   }
+}
+
+void SharedScatter::publish_scores(uint64_t k, int slot) {
+  if (!pinned_ || rank_ == 0) return;
+  const StepPlan& P = s_->plans[k % kPlanRing];
+  if (P.seq.load(std::memory_order_acquire) != k + 1) throw std::logic_error("shared scatter: plan overwritten");
+  const RankShare& sh = P.share[rank_];
+  const int64_t at = int64_t(rank_) * P.rows_per_rank;
+  if (sh.rows <= 0) return;
+  if (at + sh.rows > s_->out_floats) throw std::out_of_range("shared scatter: share outside the output");
+  std::memcpy(out(slot) + at, step_out(slot) + at, size_t(sh.rows) * sizeof(float));
 }
 
 void SharedScatter::mark_done(uint64_t k) { s_->done[rank_].store(k + 1, std::memory_order_release); }

@@ -5,7 +5,9 @@
 // With an RCCL scatter, rank 0's ONE PCIe link carries every rank's request
 // bytes and then xGMI moves them again. Here rank 0's request arenas and its
 // score outputs live in one POSIX shared-memory segment that every rank of the
-// node maps (and registers with its own GPU). Per step k:
+// node maps. A GPU reaches only host memory that its own process allocated
+// pinned, so a GPU rank moves its bytes between the segment and the device
+// through a pinned block of its own (set_pinned). Per step k:
 //
 //   rank 0   builds its batch (world x B rows) in a shared arena, then
 //            publishes the step's PLAN: for every rank r its rows
@@ -14,16 +16,18 @@
 //            share is one or two ranges)
 //   rank r   reads the plan and DMAs only its share over its OWN PCIe link
 //            into a device arena of the same layout: a patched 64-byte header
-//            (total_rows = rows_r) from private pinned memory, its slice of the
-//            row table moved to the table's start, and its payload ranges at
-//            their own offsets - so the unmodified local step kernels run on it
-//            and the head writes rank r's scores straight into rank 0's shared
-//            output at r B; then it reports step k done in the segment
+//            (total_rows = rows_r), its slice of the row table moved to the
+//            table's start, and its payload ranges at their own offsets - so
+//            the unmodified local step kernels run on it and the head writes
+//            rank r's scores at r B of the step's output (GPU ranks: staged
+//            in the pinned block on the way in, and moved from it to rank 0's
+//            shared output on the way out); then it reports step k done in
+//            the segment
 //   rank 0   answers step k once every rank reported it (bounded wait)
 //
 // Host->device bytes per rank: its share, not the whole batch; nothing crosses
 // xGMI. The RCCL scatter (parallel/fanout.py) stays the fallback (different
-// nodes, or a segment that cannot be registered).
+// nodes).
 #pragma once
 
 #include <atomic>
@@ -67,9 +71,6 @@ struct alignas(64) ScatterShared {
   alignas(64) std::atomic<uint64_t> done[kScatterMaxRanks];  // steps [0, done) finished on rank r
   std::atomic<uint32_t> attached[kScatterMaxRanks];
   StepPlan plans[kPlanRing];
-  // per (rank, slot): the patched 64-byte arena header a rank copies to its
-  // device (in the segment so that the GPU registration covers it)
-  alignas(64) uint8_t stage[kScatterMaxRanks][kScatterMaxSlots][64];
 };
 
 // One copy of a rank's share: `n` bytes from host `src` to device arena offset `dst_off`.
@@ -88,9 +89,13 @@ struct ShareCopy {
 void compute_shares(const uint8_t* arena, int64_t capacity, int64_t fields, int world, int64_t rows_per_rank,
                     RankShare* out);
 // The copies that bring `s` of `arena` into a device arena of the same layout.
-// `hdr_stage`: 64 bytes of this rank's pinned memory that receive the patched
-// header (total_rows = s.rows, GPU varint decode off).
+// `hdr_stage`: 64 bytes of this rank's memory that receive the patched header
+// (total_rows = s.rows, GPU varint decode off).
 std::vector<ShareCopy> share_copies(const uint8_t* arena, const RankShare& s, uint8_t* hdr_stage);
+// Move the copies' bytes into `staging` (an arena of `cap` bytes that the
+// device can read), each at its device offset and in the copies' order, and
+// point the copies there. Throws when a copy does not fit.
+void stage_copies(std::vector<ShareCopy>& copies, uint8_t* staging, int64_t cap);
 
 // NUMA placement of the shared arenas, per rank: requests are appended in row
 // order and shares are contiguous row ranges, so rank r's bytes of a full batch
@@ -132,11 +137,17 @@ class SharedScatter {
   uint8_t* arena(int i) const;
   float* out(int slot) const;
   int arena_index(const uint8_t* base) const;  // -1: not one of the segment's arenas
-  uint8_t* stage(int slot) const;              // this rank's header stage of a slot
   void* base() const { return base_; }
   size_t bytes() const { return bytes_; }
-  // called with (base, bytes) before the mapping goes away (e.g. hipHostUnregister)
-  void set_on_unmap(std::function<void(void*, size_t)> f) { on_unmap_ = std::move(f); }
+  // GPU ranks: `p` is pinned_bytes() of pinned host memory of this process,
+  // per slot a staging arena (the source of the share's DMA) and an output
+  // (where the step's head writes); `release` frees it with the object.
+  size_t pinned_bytes() const;
+  void set_pinned(void* p, std::function<void(void*)> release);
+  uint8_t* staging(int slot) const;  // the slot's staging arena (arena_cap bytes)
+  // Where the slot's step writes and rank 0 reads the scores: the pinned
+  // output of a GPU rank, else the shared one.
+  float* step_out(int slot) const;
   bool all_attached() const;
   void unlink();
   // create side: the per-rank slices placed at creation (empty on attach)
@@ -150,8 +161,12 @@ class SharedScatter {
   // The plan of step k (false: not published within timeout_us).
   bool wait_plan(uint64_t k, int64_t timeout_us, RankShare* mine, int* arena_idx);
   // Rank 0, once every rank finished step k on `slot`: move each rank's
-  // scores from its fixed slice (r x rows_per_rank) to its rows' place.
+  // scores from its fixed slice (r x rows_per_rank) to its rows' place
+  // (GPU rank: after bringing them from the shared output into step_out).
   void compact_scores(uint64_t k, int slot);
+  // GPU rank > 0, once its step k on `slot` finished: its scores from the
+  // pinned output into rank 0's shared output (no-op without a pinned block).
+  void publish_scores(uint64_t k, int slot);
   // This rank finished step k (its scores are in the shared output).
   void mark_done(uint64_t k);
   // Every rank finished step k (false after timeout_us; *err names the late rank).
@@ -170,7 +185,8 @@ class SharedScatter {
   uint8_t* base_ = nullptr;
   std::atomic<uint64_t> next_step_{0};
   std::atomic<int64_t> h2d_bytes_{0}, h2d_steps_{0};
-  std::function<void(void*, size_t)> on_unmap_;
+  uint8_t* pinned_ = nullptr;
+  std::function<void(void*)> release_pinned_;
   std::vector<NodeSlice> placement_;
 };
 

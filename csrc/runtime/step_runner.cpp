@@ -528,6 +528,11 @@ void StepRunner::launch_copies(int slot, void* dst, const std::vector<ShareCopy>
   used_[slot] = 1;
 }
 
+void StepRunner::wait_h2d(int slot) {
+  if (slot < 0 || slot >= int(done_.size())) throw std::out_of_range("slot");
+  if (used_[slot]) ck(hipEventSynchronize(h2d_done_[slot]), "hipEventSynchronize(h2d)");
+}
+
 void StepRunner::wait(int slot) {
   if (slot < 0 || slot >= int(done_.size())) throw std::out_of_range("slot");
   wait_slot_launched(slot);

@@ -156,6 +156,8 @@ class StepRunner {
   // skip_varint: no request of the step has packed varint ids (see launch_seq)
   void launch_program(int slot, const StepProgram& p, const void* h2d_src, int64_t h2d_bytes,
                       bool skip_varint = false);
+  // Block until the slot's last host-to-device copies have read their sources.
+  void wait_h2d(int slot);
   // Block until the slot's last step has finished (scores are on the host).
   void wait(int slot);
   // Bounded wait: false when the step has not finished within timeout_us or a

@@ -5,10 +5,10 @@ every request's candidates are split over the shards (reference
 DCNClient.java:46-74 split, :146-164 dispatch + join). Over RCCL that means
 rank 0's single PCIe link carries every rank's request bytes, then xGMI carries
 them again. With the shared arena, rank 0's request arenas and score outputs
-are one POSIX shared-memory segment that every rank of the node maps and
-registers with its own GPU: per step each rank DMAs only its share of the
-batch over its own link and writes its scores straight into rank 0's output
-(no collective in the step). Same bootstrap as the step control
+are one POSIX shared-memory segment that every rank of the node maps: per
+step each rank DMAs only its share of the batch over its own link and leaves
+its scores in rank 0's output (no collective in the step). A GPU rank moves
+both through a pinned block of its own, the only host memory its GPU reaches. Same bootstrap as the step control
 (parallel/control.py): rank 0 creates the segment under a random name,
 publishes the name in the job's store, waits for every rank to attach and
 unlinks the name.
@@ -25,9 +25,9 @@ from .control import default_store
 
 def create_shared_scatter(module, world: int, rank: int, fields: int, n_arenas: int, arena_cap: int, slots: int,
                           out_floats: int, store=None, prefix: str = "dtfs/scatter/0", node: int = -1,
-                          register: bool = False, timeout_s: float = 60.0, expected_payload: int = 0):
+                          pin: bool = False, timeout_s: float = 60.0, expected_payload: int = 0):
     """A SharedScatter of ``module`` (``_hip`` for GPU ranks, which also
-    register the mapping with their device, ``_native`` for CPU ranks).
+    get their pinned block with ``pin``, ``_native`` for CPU ranks).
     Not a collective: every rank calls it with the same ``prefix``.
     ``node``: this rank's NUMA node (-1 unknown). Every rank publishes its node;
     rank 0 places the segment on its own and, with ``expected_payload`` (bytes
@@ -48,8 +48,8 @@ def create_shared_scatter(module, world: int, rank: int, fields: int, n_arenas: 
         store.wait([name_key], datetime.timedelta(seconds=timeout_s))
         name = store.get(name_key).decode()
         seg = module.SharedScatter(name, world, rank, False)
-    if register:
-        seg.register_with_gpu()
+    if pin:
+        seg.pin_for_gpu()
     store.add(att_key, 1)
     if rank == 0:
         deadline = time.monotonic() + timeout_s
@@ -105,5 +105,5 @@ def scatter_for_engine(ctx, fields: int, arena_cap: int, slots: int, max_rows_pe
     expected = ctx.world * max_rows_per_rank * expected_row_bytes(fields, narrow_modulo, narrow_wts_cols)
     return create_shared_scatter(hip() if cuda else native(), ctx.world, ctx.rank, fields, n_arenas or slots + 3,
                                  arena_cap, slots, ctx.world * max_rows_per_rank, store=store,
-                                 prefix=f"dtfs/scatter/{tag}", node=current_node() if cuda else -1, register=cuda,
+                                 prefix=f"dtfs/scatter/{tag}", node=current_node() if cuda else -1, pin=cuda,
                                  expected_payload=expected)

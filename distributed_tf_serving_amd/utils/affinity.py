@@ -9,8 +9,8 @@ and every arena write. :func:`place_rank` runs inside the rank (not through a
 launcher wrapper): the GPU's PCI bus id -> its NUMA node (sysfs) -> every
 thread of the process bound to that node's CPUs (threads created later
 inherit) -> the thread's memory policy prefers the node; the live server then
-allocates its arenas with :func:`alloc_pinned_arena` (pages placed on the node
-before ``hipHostRegister``). ``DTFS_NUMA=0`` turns it off.
+allocates its arenas with :func:`alloc_pinned_arena` (``hipHostMalloc`` while
+the thread's memory policy binds it to the node). ``DTFS_NUMA=0`` turns it off.
 
 The reference has no host placement (a Java client against remote hosts,
 DCNClient.java:118-125).
@@ -77,8 +77,8 @@ def place_rank(device: torch.device) -> dict:
 
 def alloc_pinned_arena(nbytes: int, node: Optional[int] = None) -> torch.Tensor:
     """A pinned uint8 host buffer for a GPU live server: on this rank's NUMA
-    node when it has one (pages placed first, then hipHostRegister), else
-    torch's pinned allocator."""
+    node when it has one (hipHostMalloc bound to the node), else torch's pinned
+    allocator."""
     node = current_node() if node is None else node
     if node >= 0:
         from ..ops import hip

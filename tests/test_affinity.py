@@ -2,7 +2,7 @@
 CPU box: node discovery from sysfs, binding every thread of the process (and
 threads created later) to a CPU set, node-bound allocations (page placement
 read back with move_pages), and the no-op paths (CPU device, unknown PCI id).
-The GPU path (the GPU's bus id -> node, hipHostRegister of node-local arenas)
+The GPU path (the GPU's bus id -> node, pinned node-local arenas)
 runs in tests/test_live_gpu.py."""
 import os
 import threading

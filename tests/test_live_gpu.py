@@ -222,7 +222,7 @@ def test_one_hot_dlrm_served_from_narrow_arena_matches_eager():
 
 def test_numa_placement_and_node_local_pinned_arena():
     """utils/affinity.py on the GPU box: the GPU's PCI bus id resolves, and a
-    node-local arena is pinned (hipHostRegister) with its pages on the node;
+    node-local arena is pinned (hipHostMalloc bound to the node) with its pages on the node;
     an H2D copy from it is exact."""
     from distributed_tf_serving_amd.ops import hip
     from distributed_tf_serving_amd.utils import affinity
