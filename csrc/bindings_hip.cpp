@@ -1589,6 +1589,71 @@ torch::Tensor mlp_tail(torch::Tensor X, torch::Tensor W2p, torch::Tensor b2, int
   return y;
 }
 
+// One DCN-v2 mixture-of-low-rank-experts cross layer in one launch
+// (cross_mix.hip). Vp / Gp / Cp / Up: ops.cross_mix_pack. Returns {z, logit}
+// (undefined where not asked); `out` receives z.
+std::vector<torch::Tensor> cross_mix(torch::Tensor x0, torch::Tensor xl, torch::Tensor Vp, torch::Tensor Gp,
+                                     torch::Tensor Cp, torch::Tensor Up, torch::Tensor b, int64_t E, int64_t r,
+                                     bool want_z, c10::optional<torch::Tensor> head_w,
+                                     c10::optional<torch::Tensor> out) {
+  check_gpu(x0, "x0");
+  check_gpu(xl, "xl");
+  for (auto* t : {&Vp, &Gp, &Cp, &Up, &b}) {
+    check_dev(*t, "cross_mix operand");
+    check_same_dev(x0, *t, "cross_mix operand");
+  }
+  check_same_dev(x0, xl, "xl");
+  TORCH_CHECK(x0.scalar_type() == torch::kBFloat16 && xl.scalar_type() == torch::kBFloat16 && x0.dim() == 2 &&
+                  x0.sizes() == xl.sizes(),
+              "cross_mix: x0, xl must be bf16 [M, d] of one shape");
+  const int64_t M = x0.size(0), d = x0.size(1);
+  auto rows_ok = [&](const torch::Tensor& t) {
+    return (d == 1 || t.stride(1) == 1) && (M <= 1 || (t.stride(0) >= d && t.stride(0) % 8 == 0)) &&
+           reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+  };
+  TORCH_CHECK(rows_ok(x0) && rows_ok(xl),
+              "cross_mix: x0, xl need unit inner stride, a row stride that is a multiple of 8 and 16-byte alignment");
+  TORCH_CHECK(M < (int64_t(1) << 31), "cross_mix: row count");
+  TORCH_CHECK(d >= 64 && d % 64 == 0, "cross_mix needs d % 64 == 0, got d = ", d);
+  TORCH_CHECK(r >= 16 && r % 16 == 0, "cross_mix needs r % 16 == 0, got r = ", r);
+  TORCH_CHECK(E >= 1 && E <= 8, "cross_mix covers 1 <= E <= 8 experts, got ", E);
+  TORCH_CHECK(E * r <= 256, "cross_mix covers E * r <= 256, got ", E * r);
+  const int64_t RP = (E * r + 63) / 64 * 64;
+  for (auto* t : {&Vp, &Gp, &Cp, &Up})
+    TORCH_CHECK(t->scalar_type() == torch::kBFloat16, "cross_mix: packed weights must be bf16 (cross_mix_pack)");
+  TORCH_CHECK(Vp.numel() == RP * d && Gp.numel() == 16 * d && Cp.numel() == RP * RP && Up.numel() == d * RP,
+              "cross_mix: packed weight sizes do not match d = ", d, ", E = ", E, ", r = ", r);
+  TORCH_CHECK(b.scalar_type() == torch::kFloat32 && b.numel() == d, "cross_mix: b must be fp32 [d]");
+  if (head_w) {
+    check_dev(*head_w, "head_w");
+    check_same_dev(x0, *head_w, "head_w");
+    TORCH_CHECK(head_w->scalar_type() == torch::kFloat32 && head_w->numel() == d, "head_w must be fp32 [d]");
+  }
+  TORCH_CHECK(want_z || head_w, "cross_mix: nothing asked (want_z = False and no head_w)");
+  c10::DeviceGuard g(x0.device());
+  torch::Tensor z, logit;
+  if (want_z) {
+    if (out) {
+      check_gpu(*out, "out");
+      check_same_dev(x0, *out, "out");
+      TORCH_CHECK(out->scalar_type() == torch::kBFloat16 && out->dim() == 2 && out->sizes() == x0.sizes() &&
+                      rows_ok(*out),
+                  "cross_mix: out must be bf16 [M, d] rows like x0");
+      z = *out;
+    } else {
+      z = torch::empty({M, d}, x0.options());
+    }
+  }
+  if (head_w) logit = torch::empty({M}, x0.options().dtype(torch::kFloat32));
+  auto ld = [&](const torch::Tensor& t) { return M <= 1 ? d : t.stride(0); };
+  check_hip(dtfs::launch_cross_mix(x0.data_ptr(), ld(x0), xl.data_ptr(), ld(xl), int(M), int(d), int(E), int(r),
+                                   Vp.data_ptr(), Gp.data_ptr(), Cp.data_ptr(), Up.data_ptr(), b.data_ptr<float>(),
+                                   head_w ? head_w->data_ptr<float>() : nullptr, want_z ? z.data_ptr() : nullptr,
+                                   want_z ? ld(z) : d, head_w ? logit.data_ptr<float>() : nullptr, cur_stream(x0)),
+            "cross_mix");
+  return {z, logit};
+}
+
 // The same tail on the block-scaled fp8 matrix cores (mlp_tail_fp8.hip): the
 // kernel MX-quantises X and h2 itself. W2p / W3p: e4m3 weights in the 16x16x128
 // fragment order (ops.pack_bfrag_fp8); sw2 / sw3: per-output-channel scales.
@@ -2475,6 +2540,10 @@ PYBIND11_MODULE(_hip, m) {
   m.def("mlp_tail", &mlp_tail, py::arg("X"), py::arg("W2p"), py::arg("b2"), py::arg("act2"), py::arg("W3p"),
         py::arg("b3"), py::arg("act3"), py::arg("hw"), py::arg("hbias") = 0.0, py::arg("extra") = py::none(),
         py::arg("sigmoid") = true, py::arg("out") = py::none());
+  m.def("cross_mix", &cross_mix, py::arg("x0"), py::arg("xl"), py::arg("Vp"), py::arg("Gp"), py::arg("Cp"),
+        py::arg("Up"), py::arg("b"), py::arg("E"), py::arg("r"), py::arg("want_z") = true,
+        py::arg("head_w") = py::none(), py::arg("out") = py::none(),
+        "DCN-v2 mixture-of-low-rank-experts cross layer in one launch (cross_mix.hip) -> [z, logit]");
   m.def("mlp_tail_fp8", &mlp_tail_fp8, py::arg("X"), py::arg("W2p"), py::arg("sw2"), py::arg("b2"), py::arg("act2"),
         py::arg("W3p"), py::arg("sw3"), py::arg("b3"), py::arg("act3"), py::arg("hw"), py::arg("hbias") = 0.0,
         py::arg("extra") = py::none(), py::arg("sigmoid") = true, py::arg("out") = py::none(),

@@ -171,6 +171,18 @@ hipError_t launch_mlp_tail(const void* X, int64_t ldx, int M, int K1, const void
                            int N2, const void* W3p, const float* b3, int act3, int N3, const float* hw, float hbias,
                            const float* extra, int extra_n, int64_t extra_ld, int out_act, float* y, hipStream_t st);
 
+// DCN-v2 mixture of low-rank cross experts, one layer per launch (cross_mix.hip):
+// a = tanh(V xl), p = softmax(G xl), h = concat_i(p_i tanh(C_i a_i)),
+// z = bf16(x0 * (U h + b) + xl), logit[m] = sum_j float(z[m, j]) hw[j].
+// x0 / xl / z: bf16 rows, unit inner stride, ld in elements (multiples of 8),
+// 16-byte aligned. Vp / Gp / Cp / Up: ops.cross_mix_pack (R_pad = E r rounded up
+// to 64; G padded to 16 rows; C block-diagonal [R_pad, R_pad]; U's rows permuted
+// inside every 32-row group). d % 64 == 0, r % 16 == 0, 1 <= E <= 8, E r <= 256.
+// z and / or logit may be null (logit needs hw); rows past M are never written.
+hipError_t launch_cross_mix(const void* x0, int64_t ld0, const void* xl, int64_t ldl, int M, int d, int E, int r,
+                            const void* Vp, const void* Gp, const void* Cp, const void* Up, const float* bias,
+                            const float* hw, void* z, int64_t ldz, float* logit, hipStream_t st);
+
 // The same tail on the block-scaled fp8 matrix cores (mlp_tail_fp8.hip): x
 // (bf16) and the fp32 h2 are MX-quantised inside the kernel (e4m3 + one E8M0
 // byte per 32 columns), W2p / W3p are e4m3 weights in the fragment order of

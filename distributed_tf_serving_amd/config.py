@@ -44,6 +44,10 @@ class ModelConfig:
     mlp_dims: Tuple[int, ...] = (1024, 512, 256)
     num_cross_layers: int = 3         # dcn / dcn_v2
     cross_rank: int = 0               # dcn_v2: 0 = full-rank W, >0 = low-rank U V^T
+    # dcn_v2: >= 1 = every cross layer is a softmax-gated mixture of this many rank-cross_rank experts
+    # (ops.cross_mix; cross_rank % 16 == 0, <= 8 experts, cross_experts * cross_rank <= 256, bf16) - checked
+    # when the model is built; 0 = the plain full-rank / low-rank layer
+    cross_experts: int = 0
     num_dense: int = 13               # dlrm: leading fields carried as dense values
     bottom_mlp: Tuple[int, ...] = (512, 256, 64)   # dlrm bottom MLP (last = embed_dim)
     table_rows: int = 1_000_000       # dlrm: rows per sparse table

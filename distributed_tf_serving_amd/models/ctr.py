@@ -33,7 +33,7 @@ from torch import nn
 
 from .. import ops
 from ..config import ModelConfig
-from .layers import DTYPES, MLP, Dense, hashed_uniform_rows_, init_uniform_, make_generator, pad8
+from .layers import DTYPES, MLP, CrossMix, Dense, hashed_uniform_rows_, init_uniform_, make_generator, pad8
 
 
 class CTRModel(nn.Module):
@@ -321,7 +321,10 @@ class DCN(CTRModel):
 
 
 class DCNv2(CTRModel):
-    """DCN-v2: full-rank (or low-rank) matrix cross layers; optional fp8 towers."""
+    """DCN-v2: full-rank (or low-rank) matrix cross layers; optional fp8 towers.
+    ``cross_experts >= 1`` (with ``cross_rank`` = r > 0): every cross layer is a
+    softmax-gated mixture of that many rank-r experts, one ops.cross_mix launch
+    per layer (bf16; with gemm_dtype fp8 only the MLP is fp8)."""
 
     family = "dcn_v2"
     supports_arena = True
@@ -334,7 +337,17 @@ class DCNv2(CTRModel):
         self.fp8 = cfg.gemm_dtype == "fp8"
         self.emb = self._embedding_table(V, D)
         self.low_rank = cfg.cross_rank > 0
-        if self.low_rank:
+        self.mix = cfg.cross_experts >= 1
+        if cfg.cross_experts < 0 or (self.mix and not self.low_rank):
+            raise ValueError(f"cross_experts = {cfg.cross_experts} needs cross_experts >= 0 and, for a mixture, "
+                             f"cross_rank > 0 (got {cfg.cross_rank})")
+        if self.mix:
+            if self.dtype != torch.bfloat16:
+                raise ValueError("cross_experts needs param_dtype: bf16")
+            # ValueError naming the limit when (d, E, r) is outside what the kernel covers
+            self.cross_mix = nn.ModuleList([CrossMix(d, cfg.cross_experts, cfg.cross_rank, self.dtype, self.device_,
+                                                     self.gen) for _ in range(L)])
+        elif self.low_rank:
             r = pad8(cfg.cross_rank)
             self.cross_v = nn.ModuleList([Dense(d, r, "none", self.dtype, self.device_, self.gen, fp8=self.fp8)
                                           for _ in range(L)])
@@ -402,6 +415,12 @@ class DCNv2(CTRModel):
         """The cross layers -> the cross half of the head logit."""
         fp8_full = self.fp8 and not self.low_rank
         L = self.cfg.num_cross_layers
+        if self.mix and L > 0:
+            # L launches; the last one reduces the cross logit instead of writing z
+            xl = x0
+            for layer in self.cross_mix[:-1]:
+                xl, _ = layer(x0, xl)
+            return self.cross_mix[-1](x0, xl, want_z=False, head_w=self.head_wc)[1]
         if fp8_full and self.d % 8 == 0 and L > 0:
             # split cross layers: plain-epilogue GEMM y = xl W^T + b (the
             # 8-phase tile runs it) + one combine pass that writes z = x0*y + xl,

@@ -157,6 +157,53 @@ class Dense(nn.Module):
         return ops.linear(x, self.weight, self.bias, self.act)
 
 
+class CrossMix(nn.Module):
+    """One DCN-v2 cross layer as a softmax-gated mixture of ``experts`` low-rank
+    experts (ops.cross_mix): V [E r, d], G [E, d], C [E, r, r], U [d, E r]
+    bf16, b fp32 [d]."""
+
+    def __init__(self, d: int, experts: int, rank: int, dtype, device, gen):
+        super().__init__()
+        ops.cross_mix_check(d, experts, rank)
+        self.d, self.experts, self.rank = d, experts, rank
+        R = experts * rank
+
+        def w(shape, fan_in, fan_out, gain=1.0):
+            t = init_uniform_(torch.empty(*shape, device=device), gain * math.sqrt(6.0 / (fan_in + fan_out)), gen)
+            return nn.Parameter(t.to(dtype), requires_grad=False)
+
+        self.V = w((R, d), d, R)
+        self.G = w((experts, d), d, experts)
+        self.C = w((experts, rank, rank), rank, rank)
+        self.U = w((d, R), R, d, 0.5)  # as the full-rank layers: keep the stacked product well-conditioned
+        self.bias = nn.Parameter(init_uniform_(torch.empty(d, dtype=torch.float32, device=device), 0.01, gen),
+                                 requires_grad=False)
+
+    def raw(self):
+        return self.V, self.G, self.C, self.U
+
+    def packed(self) -> tuple:
+        """ops.cross_mix_pack of the weights, re-packed INTO the same buffers
+        whenever one of them changed (captured HIP graphs read those buffers;
+        see Dense.packed)."""
+        key = tuple((t.data_ptr(), t._version) for t in self.raw())
+        cached = self.__dict__.get("_packed")
+        if cached is None or cached[0] != key:
+            fresh = ops.cross_mix_pack(*(t.detach() for t in self.raw()))
+            if cached is not None and all(o.shape == n.shape and o.device == n.device
+                                          for o, n in zip(cached[1][:4], fresh[:4])):
+                for o, n in zip(cached[1][:4], fresh[:4]):
+                    o.copy_(n)
+                fresh = cached[1]
+            cached = (key, fresh)
+            self.__dict__["_packed"] = cached
+        return cached[1]
+
+    def forward(self, x0: torch.Tensor, xl: torch.Tensor, want_z: bool = True, head_w=None):
+        return ops.cross_mix(x0, xl, self.packed() if x0.is_cuda else self.raw(), self.bias, want_z=want_z,
+                             head_w=head_w)
+
+
 class MLP(nn.Module):
     def __init__(self, in_dim: int, dims: Sequence[int], dtype, device, gen, fp8: bool = False,
                  last_act: str = "relu", in_pad: Optional[int] = None, tail_fp8: bool = False):

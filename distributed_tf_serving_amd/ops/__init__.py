@@ -940,6 +940,94 @@ def gather_mlp(table: torch.Tensor, ids, wts: Optional[torch.Tensor], lin: Optio
                             int(ids.shape[1]), m, float(bias), *args)
 
 
+def cross_mix_check(d: int, E: int, r: int) -> None:
+    """The range csrc/kernels/cross_mix.hip covers; ValueError names the limit."""
+    if d < 64 or d % 64:
+        raise ValueError(f"cross_mix needs d % 64 == 0, got d = {d}")
+    if r < 16 or r % 16:
+        raise ValueError(f"cross_mix needs a rank r % 16 == 0, got r = {r}")
+    if not 1 <= E <= 8:
+        raise ValueError(f"cross_mix covers 1 <= E <= 8 experts, got E = {E}")
+    if E * r > 256:
+        raise ValueError(f"cross_mix covers E * r <= 256, got E * r = {E * r}")
+
+
+def _cross_mix_dims(V, G, C, U):
+    E, r = (int(C.shape[0]), int(C.shape[1])) if C.dim() == 3 else (0, 0)
+    d = int(V.shape[-1])
+    if (C.dim() != 3 or tuple(C.shape) != (E, r, r) or tuple(V.shape) != (E * r, d) or tuple(G.shape) != (E, d)
+            or tuple(U.shape) != (d, E * r)):
+        raise ValueError(f"cross_mix weights: V [E r, d], G [E, d], C [E, r, r], U [d, E r]; got "
+                         f"{tuple(V.shape)}, {tuple(G.shape)}, {tuple(C.shape)}, {tuple(U.shape)}")
+    cross_mix_check(d, E, r)
+    return d, E, r
+
+
+def cross_mix_pack(V: torch.Tensor, G: torch.Tensor, C: torch.Tensor, U: torch.Tensor) -> tuple:
+    """The mixture cross layer's weights as csrc/kernels/cross_mix.hip reads
+    them -> (Vp, Gp, Cp, Up, E, r), all :func:`pack_bfrag` order with
+    R_pad = E r rounded up to 64 and zero padding: V [R_pad, d]; G as one
+    16-row block; C block-diagonal [R_pad, R_pad]; U [d, R_pad] with its rows
+    permuted inside every 32-row group (block t, row 4 q + s = U row
+    8 q + 4 t + s: a lane's MFMA outputs are then 8 consecutive columns)."""
+    d, E, r = _cross_mix_dims(V, G, C, U)
+    R = E * r
+    RP = -(-R // 64) * 64
+    z = lambda *s: torch.zeros(*s, dtype=torch.bfloat16, device=V.device)  # noqa: E731
+    Vz, Gz, Cz, Uz = z(RP, d), z(16, d), z(RP, RP), z(d, RP)
+    Vz[:R] = V
+    Gz[:E] = G
+    Cz[:R, :R] = torch.block_diag(*C.to(torch.bfloat16))
+    Uz[:, :R] = U
+    Uz = Uz.reshape(d // 32, 4, 2, 4, RP).permute(0, 2, 1, 3, 4).reshape(d, RP)
+    return pack_bfrag(Vz), pack_bfrag(Gz), pack_bfrag(Cz), pack_bfrag(Uz), E, r
+
+
+def cross_mix(x0: torch.Tensor, xl: torch.Tensor, weights, b: torch.Tensor, want_z: bool = True,
+              head_w: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
+    """DCN-v2 cross layer as a softmax-gated mixture of E low-rank experts
+    ("DCN-Mix"), one launch (csrc/kernels/cross_mix.hip). With R = E r and
+    slice i = columns i r .. i r + r - 1:
+
+        a = tanh(V xl)   p = softmax(G xl)   c_i = tanh(C_i a_i)
+        z = sum_i p_i x0 * (U_i c_i + b) + xl  =  x0 * (U concat_i(p_i c_i) + b) + xl
+
+    ``weights``: :func:`cross_mix_pack`'s tuple (GPU) or the raw
+    (V [R, d], G [E, d], C [E, r, r], U [d, R]) bf16 (packed here on the GPU,
+    required on the CPU). ``b`` fp32 [d]. Returns (z or None, logit or None),
+    logit = z . head_w (fp32 [M], a head ``extra``). ``out`` receives z.
+
+    Rounding: every matrix product accumulates in fp32; gate logits, softmax
+    and both tanh are fp32; ``a`` is rounded to bf16 after the first tanh and
+    h = p_i c_i after the gate scaling (both are MFMA operands); y = U h + b
+    stays fp32; z = bf16(x0 y + xl); the logit sums float(z_j) head_w_j in
+    fp32 over the rounded z, so both forms of the call agree."""
+    if not want_z and head_w is None:
+        raise ValueError("cross_mix: nothing asked (want_z = False and no head_w)")
+    raw = len(weights) == 4
+    if x0.is_cuda:
+        Vp, Gp, Cp, Up, E, r = cross_mix_pack(*weights) if raw else weights
+        z, logit = hip().cross_mix(x0, xl, Vp, Gp, Cp, Up, b, int(E), int(r), want_z, head_w, out)
+        return (z if want_z else None), (logit if head_w is not None else None)
+    if not raw:
+        raise ValueError("cross_mix on the CPU takes the raw (V, G, C, U)")
+    V, G, C, U = weights
+    d, E, r = _cross_mix_dims(V, G, C, U)
+    M = x0.shape[0]
+    xf = xl.float()
+    a = torch.tanh(xf @ V.float().t()).to(torch.bfloat16).float()
+    p = torch.softmax(xf @ G.float().t(), dim=1)
+    c = torch.tanh(torch.einsum("mek,enk->men", a.view(M, E, r), C.float()))
+    h = (c * p[:, :, None]).reshape(M, E * r).to(torch.bfloat16).float()
+    y = h @ U.float().t() + b.float()
+    zb = (x0.float() * y + xf).to(torch.bfloat16)
+    logit = zb.float() @ head_w.float() if head_w is not None else None
+    if want_z and out is not None:
+        out.copy_(zb)
+        zb = out
+    return (zb if want_z else None), logit
+
+
 def unpack_bfrag(Wp: torch.Tensor, N: int, K: int) -> torch.Tensor:
     """Inverse of :func:`pack_bfrag` (tests)."""
     return Wp.reshape(N // 16, K // 64, 2, 4, 16, 8).permute(0, 4, 1, 2, 3, 5).reshape(N, K)
