@@ -804,6 +804,106 @@ torch::Tensor dot_interaction_gather_fp8_arena(torch::Tensor dense, torch::Tenso
   return dot_interaction_gather_fp8_impl(dense, codes, scale, nullptr, &arena, id_col0, modulo_f, offset_f, out_cols);
 }
 
+// K1b + K5 (interaction_bag.hip): the multi-hot bag pooling inside the dot
+// interaction. table: bf16 [V, 64], or e4m3 codes with scale fp32 [T]. ids /
+// wts: [B, T * hot] row views (wts optional: every weight 1), or a device
+// request arena whose features id_col0 .. id_col0 + T * hot - 1 they are.
+static torch::Tensor dot_interaction_bag_impl(torch::Tensor dense, torch::Tensor table, const torch::Tensor* scale,
+                                              const torch::Tensor* ids, const c10::optional<torch::Tensor>& wts,
+                                              const torch::Tensor* arena, int64_t id_col0, int64_t hot,
+                                              torch::Tensor modulo_f, torch::Tensor offset_f, int64_t out_cols) {
+  check_dev(dense, "dense");
+  TORCH_CHECK(dense.scalar_type() == torch::kBFloat16, "dense must be bf16");
+  TORCH_CHECK(dense.dim() == 2 && dense.size(1) == 64 && dense.stride(1) == 1 && dense.stride(0) % 8 == 0 &&
+                  dense.stride(0) >= 64,
+              "dense must be [B, 64] with unit inner stride");
+  const int64_t B = dense.size(0), T = modulo_f.numel();
+  TORCH_CHECK(T >= 1 && T + 1 <= 32, "dot interaction kernel handles 1 <= T <= 31 tables");
+  TORCH_CHECK(hot >= 2 && T * hot <= 512, "bag interaction kernel handles hot >= 2 and T * hot <= 512 ids per row");
+  if (scale) {
+    check_fp8_table(dense, table, *scale, T);
+  } else {
+    check_same_dev(dense, table, "table");
+    TORCH_CHECK(table.scalar_type() == torch::kBFloat16 && table.dim() == 2 && table.size(1) == 64 &&
+                    table.is_contiguous() && table.size(0) >= 1,
+                "table must be contiguous bf16 [V, 64]");
+  }
+  for (auto* t : {&modulo_f, &offset_f}) {
+    check_same_dev(dense, *t, "table map");
+    TORCH_CHECK(t->scalar_type() == torch::kInt64 && t->numel() == T && t->is_contiguous(), "modulo_f / offset_f: int64 [T]");
+  }
+  const float* wp = nullptr;
+  int64_t ldw = 0;
+  if (ids) {
+    check_same_dev(dense, *ids, "ids");
+    TORCH_CHECK((ids->scalar_type() == torch::kInt64 || ids->scalar_type() == torch::kInt32) && ids->dim() == 2 &&
+                    ids->stride(1) == 1 && ids->size(0) == B && ids->size(1) == T * hot && ids->stride(0) >= T * hot,
+                "ids must be int32/int64 [B, T * hot] rows with unit inner stride");
+    if (wts) {
+      check_same_dev(dense, *wts, "wts");
+      TORCH_CHECK(wts->scalar_type() == torch::kFloat32 && wts->dim() == 2 && wts->stride(1) == 1 &&
+                      wts->size(0) == B && wts->size(1) == T * hot && wts->stride(0) >= T * hot,
+                  "wts must be fp32 [B, T * hot] rows with unit inner stride");
+      wp = wts->data_ptr<float>();
+      ldw = wts->stride(0);
+    }
+  } else {
+    check_same_dev(dense, *arena, "arena");
+    TORCH_CHECK(arena->scalar_type() == torch::kUInt8 && arena->is_contiguous() &&
+                    arena->numel() > dtfs::kArenaPayloadOff,
+                "arena must be a contiguous uint8 request arena");
+    TORCH_CHECK(id_col0 >= 0, "id_col0 >= 0");
+  }
+  const int64_t used = 64 + (T + 1) * T / 2;
+  if (out_cols <= 0) out_cols = (used + 7) / 8 * 8;
+  TORCH_CHECK(out_cols >= used && out_cols % 8 == 0 && out_cols <= 1024, "out_cols: >= used, a multiple of 8, <= 1024");
+  c10::DeviceGuard g(dense.device());
+  auto out = torch::empty({B, out_cols}, dense.options());
+  const void* ip = ids ? ids->data_ptr() : nullptr;
+  const bool ids64 = ids ? ids->scalar_type() == torch::kInt64 : true;
+  const int64_t ldi = ids ? ids->stride(0) : 0;
+  const void* ap = arena ? arena->data_ptr() : nullptr;
+  if (scale)
+    check_hip(dtfs::launch_dot_interaction_bag_fp8(dense.data_ptr(), dense.stride(0), table.data_ptr(), table.size(0),
+                                                   scale->data_ptr<float>(), ip, ids64, ldi, wp, ldw, int(hot),
+                                                   modulo_f.data_ptr<int64_t>(), offset_f.data_ptr<int64_t>(), int(T),
+                                                   int(B), out.data_ptr(), out_cols, int(out_cols), cur_stream(dense),
+                                                   ap, int(id_col0)),
+              "dot_interaction_bag_fp8");
+  else
+    check_hip(dtfs::launch_dot_interaction_bag(dense.data_ptr(), dense.stride(0), table.data_ptr(), table.size(0), ip,
+                                               ids64, ldi, wp, ldw, int(hot), modulo_f.data_ptr<int64_t>(),
+                                               offset_f.data_ptr<int64_t>(), int(T), int(B), out.data_ptr(), out_cols,
+                                               int(out_cols), cur_stream(dense), ap, int(id_col0)),
+              "dot_interaction_bag");
+  return out;
+}
+
+torch::Tensor dot_interaction_bag(torch::Tensor dense, torch::Tensor table, torch::Tensor ids,
+                                  c10::optional<torch::Tensor> wts, int64_t hot, torch::Tensor modulo_f,
+                                  torch::Tensor offset_f, int64_t out_cols) {
+  return dot_interaction_bag_impl(dense, table, nullptr, &ids, wts, nullptr, 0, hot, modulo_f, offset_f, out_cols);
+}
+
+torch::Tensor dot_interaction_bag_arena(torch::Tensor dense, torch::Tensor table, torch::Tensor arena, int64_t id_col0,
+                                        int64_t hot, torch::Tensor modulo_f, torch::Tensor offset_f, int64_t out_cols) {
+  return dot_interaction_bag_impl(dense, table, nullptr, nullptr, c10::nullopt, &arena, id_col0, hot, modulo_f,
+                                  offset_f, out_cols);
+}
+
+torch::Tensor dot_interaction_bag_fp8(torch::Tensor dense, torch::Tensor codes, torch::Tensor scale, torch::Tensor ids,
+                                      c10::optional<torch::Tensor> wts, int64_t hot, torch::Tensor modulo_f,
+                                      torch::Tensor offset_f, int64_t out_cols) {
+  return dot_interaction_bag_impl(dense, codes, &scale, &ids, wts, nullptr, 0, hot, modulo_f, offset_f, out_cols);
+}
+
+torch::Tensor dot_interaction_bag_fp8_arena(torch::Tensor dense, torch::Tensor codes, torch::Tensor scale,
+                                            torch::Tensor arena, int64_t id_col0, int64_t hot, torch::Tensor modulo_f,
+                                            torch::Tensor offset_f, int64_t out_cols) {
+  return dot_interaction_bag_impl(dense, codes, &scale, nullptr, c10::nullopt, &arena, id_col0, hot, modulo_f,
+                                  offset_f, out_cols);
+}
+
 // K1b on fp8 tables: bag b reads table b % T's scale (scale fp32 [T])
 torch::Tensor embedding_bag_fp8(torch::Tensor codes, torch::Tensor scale, torch::Tensor idx, torch::Tensor offsets,
                                 c10::optional<torch::Tensor> psw, int64_t modulo, bool mean, bool out_bf16,
@@ -2571,6 +2671,17 @@ PYBIND11_MODULE(_hip, m) {
   m.def("dot_interaction_gather_fp8_arena", &dot_interaction_gather_fp8_arena, py::arg("dense"), py::arg("emb_q"),
         py::arg("emb_scale"), py::arg("arena"), py::arg("id_col0"), py::arg("modulo_f"), py::arg("offset_f"),
         py::arg("out_cols") = 0);
+  m.def("dot_interaction_bag", &dot_interaction_bag, py::arg("dense"), py::arg("table"), py::arg("ids"),
+        py::arg("wts"), py::arg("hot"), py::arg("modulo_f"), py::arg("offset_f"), py::arg("out_cols") = 0,
+        "K1b + K5: multi-hot bag pooling inside the dot interaction (interaction_bag.hip)");
+  m.def("dot_interaction_bag_arena", &dot_interaction_bag_arena, py::arg("dense"), py::arg("table"), py::arg("arena"),
+        py::arg("id_col0"), py::arg("hot"), py::arg("modulo_f"), py::arg("offset_f"), py::arg("out_cols") = 0);
+  m.def("dot_interaction_bag_fp8", &dot_interaction_bag_fp8, py::arg("dense"), py::arg("emb_q"), py::arg("emb_scale"),
+        py::arg("ids"), py::arg("wts"), py::arg("hot"), py::arg("modulo_f"), py::arg("offset_f"),
+        py::arg("out_cols") = 0);
+  m.def("dot_interaction_bag_fp8_arena", &dot_interaction_bag_fp8_arena, py::arg("dense"), py::arg("emb_q"),
+        py::arg("emb_scale"), py::arg("arena"), py::arg("id_col0"), py::arg("hot"), py::arg("modulo_f"),
+        py::arg("offset_f"), py::arg("out_cols") = 0);
   m.def("embedding_bag_fp8", &embedding_bag_fp8, py::arg("emb_q"), py::arg("emb_scale"), py::arg("indices"),
         py::arg("offsets"), py::arg("per_sample_weights") = py::none(), py::arg("modulo") = 0, py::arg("mean") = false,
         py::arg("out_bf16") = false, py::arg("out") = py::none(),

@@ -334,6 +334,26 @@ hipError_t launch_dot_interaction_gather_fp8(const void* dense, int64_t ldd, con
                                              int64_t ldo, int out_cols, hipStream_t st, const void* arena = nullptr,
                                              int id_col0 = 0);
 
+// K1b + K5 (interaction_bag.hip): the multi-hot DLRM step on local tables in
+// one launch. Vector t + 1 of row b is bf16(sum_{j < hot} w(b, t hot + j) *
+// table[offset_f[t] + id(b, t hot + j) mod modulo_f[t]]), fp32 accumulation in
+// id order; ids / wts are [B][>= T hot] row views (wts == nullptr: every
+// weight 1), or with arena the features id_col0 .. id_col0 + T hot - 1 of arena
+// row b and their weights. 1 <= T <= 31, hot >= 2, T hot <= 512; out as above.
+hipError_t launch_dot_interaction_bag(const void* dense, int64_t ldd, const void* table, int64_t table_rows,
+                                      const void* ids, bool ids64, int64_t ldi, const float* wts, int64_t ldw, int hot,
+                                      const int64_t* modulo_f, const int64_t* offset_f, int T, int B, void* out,
+                                      int64_t ldo, int out_cols, hipStream_t st, const void* arena = nullptr,
+                                      int id_col0 = 0);
+
+// The same on fp8 tables (codes + one power-of-two scale per table): bit-equal
+// to launch_dot_interaction_bag on the dequantised table.
+hipError_t launch_dot_interaction_bag_fp8(const void* dense, int64_t ldd, const void* codes, int64_t table_rows,
+                                          const float* scale, const void* ids, bool ids64, int64_t ldi,
+                                          const float* wts, int64_t ldw, int hot, const int64_t* modulo_f,
+                                          const int64_t* offset_f, int T, int B, void* out, int64_t ldo, int out_cols,
+                                          hipStream_t st, const void* arena = nullptr, int id_col0 = 0);
+
 // K1b on fp8 tables (D = 64): launch_embedding_bag with e4m3 codes; bag b
 // takes scale[b % T] (bags laid out [B][T]). modulo in [1, table_rows].
 hipError_t launch_embedding_bag_fp8(const void* codes, int64_t table_rows, const float* scale, int T, const void* idx,

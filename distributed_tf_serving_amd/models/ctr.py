@@ -664,12 +664,22 @@ class DLRM(CTRModel):
         requests carry just those (serving/live.py); 0 = all."""
         return self.cfg.num_dense if self.hot == 1 else 0
 
+    # multi-hot on local tables: pool the bags inside the interaction kernel
+    # (ops.dot_interaction_bag*); False keeps lookup() + interact_and_top()
+    # (the A/B study, tests)
+    use_bag_interaction = True
+
+    def _bag_fused(self) -> bool:
+        return self.use_bag_interaction and ops.bag_interaction_fits(self.T, self.hot)
+
     @property
     def supports_arena(self) -> bool:
-        """One-hot, local tables, the fused bottom tower: the step reads the
-        request arena itself (no unpack pass: K0 fused into the bottom MLP
-        and the interaction's gather)."""
-        return self.hot == 1 and (self.emb is not None or self.emb_q is not None) and self._bottom_fused()
+        """Local tables, the fused bottom tower, one-hot or a multi-hot shape
+        the bag-interaction kernel serves: the step reads the request arena
+        itself (no unpack pass: K0 fused into the bottom MLP and the
+        interaction's gather / bag pooling)."""
+        return ((self.hot == 1 or self._bag_fused()) and (self.emb is not None or self.emb_q is not None)
+                and self._bottom_fused())
 
     # (no resolve lane: step k+1's bottom MLP + gathered interaction on the
     # aux lane beside step k's top MLP measured slower, 100.2 / 100.5 vs
@@ -690,6 +700,19 @@ class DLRM(CTRModel):
             z = ops.dot_interaction_gather_fp8(dense_out, self.emb_q, self.emb_scale,
                                                ids if arena else self.sparse_ids(ids), self.modulo_f, self.offset_f,
                                                self.inter_cols, id_col0=self.cfg.num_dense)
+            return self.top.forward_head(z, self.head_w, self.head_b, out=out)
+        local = self.emb is not None or self.emb_q is not None
+        if self.hot > 1 and local and self._bag_fused() and (arena or (ids.is_cuda and wts.dtype == torch.float32)):
+            # multi-hot, local tables: one kernel pools the bags and interacts, ids and
+            # weights read in place (no pack_ids, weight copy, offsets or [B, T, 64] buffer)
+            nd = self.cfg.num_dense
+            sp, w = (ids, None) if arena else (self.sparse_ids(ids), wts[:, nd:])
+            if self.emb is not None:
+                z = ops.dot_interaction_bag(dense_out, self.emb, sp, w, self.hot, self.modulo_f, self.offset_f,
+                                            self.inter_cols, id_col0=nd)
+            else:
+                z = ops.dot_interaction_bag_fp8(dense_out, self.emb_q, self.emb_scale, sp, w, self.hot, self.modulo_f,
+                                                self.offset_f, self.inter_cols, id_col0=nd)
             return self.top.forward_head(z, self.head_w, self.head_b, out=out)
         emb = self.lookup(ids, wts)
         return self.interact_and_top(dense_out, emb, out=out)

@@ -14,7 +14,8 @@ Op inventory: K0 ``pack_ids``, K1 ``embed``, K1b
 ``cross_v2`` / ``linear_fp8``, K4 ``linear``, K5 ``dot_interaction``, K6
 ``head``, K4+K6 ``linear_head``, K4+K4+K6 ``mlp_tail`` / ``mlp_tail_fp8``, K7 ``sort_scores``, K7s ``rank_segments`` /
 ``rank_arena``; on fp8 tables K1+K5 ``dot_interaction_gather_fp8`` and K1b
-``embedding_bag_fp8``; through the peer lookup ``dot_interaction_gather_peer`` /
+``embedding_bag_fp8``; K1b+K5 ``dot_interaction_bag`` / ``dot_interaction_bag_fp8``
+(multi-hot bags pooled inside the interaction); through the peer lookup ``dot_interaction_gather_peer`` /
 ``peer_bag`` (bf16 or fp8 stores, by the peer tables' dtype).
 """
 from __future__ import annotations
@@ -585,6 +586,75 @@ def dot_interaction_gather_fp8(dense: torch.Tensor, emb_q: torch.Tensor, emb_sca
     rows = _hash_rows(ids, 0, modulo_f, offset_f).clamp(0, emb_q.shape[0] - 1)
     tables = torch.arange(T).view(1, T).expand_as(rows)
     return dot_interaction(dense, dequant_table_fp8(emb_q, emb_scale, rows, tables), out_cols)
+
+
+# ------------------------------------------------------------------ K1b + K5
+BAG_INTERACT_MAX_IDS = 512  # T * hot staged per candidate (csrc/kernels/interaction_bag.hip kBagStage)
+
+
+def bag_interaction_fits(T: int, hot: int) -> bool:
+    """Shapes the fused bag-interaction kernels serve."""
+    return 1 <= T <= 31 and hot >= 2 and T * hot <= BAG_INTERACT_MAX_IDS
+
+
+def _bag_inputs(ids, wts, T: int, hot: int, id_col0: int):
+    """(ids, wts) of the CPU reference: an arena is unpacked, its columns id_col0 .. + T * hot taken."""
+    if isinstance(ids, ArenaRows):
+        ids, wts = (t[:, id_col0:id_col0 + T * hot] for t in _arena_unpack_host(ids))
+    return ids, wts
+
+
+def _bag_pool_cpu(vals: torch.Tensor, wts: Optional[torch.Tensor], T: int, hot: int, dtype) -> torch.Tensor:
+    """fp32 rows [B, T * hot, D] -> weighted sum over each table's hot rows, rounded to ``dtype`` [B, T, D]."""
+    if wts is not None:
+        vals = vals * wts.float().unsqueeze(-1)
+    return vals.view(vals.shape[0], T, hot, -1).sum(2).to(dtype)
+
+
+def dot_interaction_bag(dense: torch.Tensor, table: torch.Tensor, ids, wts: Optional[torch.Tensor], hot: int,
+                        modulo_f: torch.Tensor, offset_f: torch.Tensor, out_cols: int = 0,
+                        id_col0: int = 0) -> torch.Tensor:
+    """K1b fused into K5 (multi-hot DLRM, local tables): dot_interaction(dense,
+    pooled) with pooled[b, t] = bf16(sum_j wts[b, t hot + j] * table[offset_f[t]
+    + ids[b, t hot + j] mod modulo_f[t]]), without pack_ids, the CSR offsets or
+    the [B, T, 64] buffer (csrc/kernels/interaction_bag.hip). ``ids``:
+    int32/int64 [B, T * hot] rows (a row view is fine) with ``wts`` fp32 rows of
+    the same shape or None (all 1), or :class:`ArenaRows` whose features
+    id_col0 .. id_col0 + T * hot - 1 carry both. CPU: plain fp32 math."""
+    T, hot = int(modulo_f.numel()), int(hot)
+    if out_cols <= 0:
+        out_cols = interaction_cols(T, dense.shape[1])
+    if isinstance(ids, ArenaRows) and ids.arena.is_cuda:
+        return hip().dot_interaction_bag_arena(dense, table, ids.arena, int(id_col0), hot, modulo_f, offset_f,
+                                               int(out_cols))
+    ids, wts = _bag_inputs(ids, wts, T, hot, id_col0)
+    if dense.is_cuda:
+        return hip().dot_interaction_bag(dense, table, _rows(ids), None if wts is None else _rows(wts), hot, modulo_f,
+                                         offset_f, int(out_cols))
+    rows = _hash_rows(ids, 0, modulo_f.repeat_interleave(hot), offset_f.repeat_interleave(hot))
+    vals = table[rows.clamp(0, table.shape[0] - 1)].float()
+    return dot_interaction(dense, _bag_pool_cpu(vals, wts, T, hot, table.dtype), out_cols)
+
+
+def dot_interaction_bag_fp8(dense: torch.Tensor, emb_q: torch.Tensor, emb_scale: torch.Tensor, ids,
+                            wts: Optional[torch.Tensor], hot: int, modulo_f: torch.Tensor, offset_f: torch.Tensor,
+                            out_cols: int = 0, id_col0: int = 0) -> torch.Tensor:
+    """:func:`dot_interaction_bag` on fp8 tables (``emb_q`` float8_e4m3fn [V, 64]
+    codes, ``emb_scale`` fp32 [T]): bit-equal to it on the dequantised table."""
+    T, hot = int(modulo_f.numel()), int(hot)
+    if out_cols <= 0:
+        out_cols = interaction_cols(T, dense.shape[1])
+    if isinstance(ids, ArenaRows) and ids.arena.is_cuda:
+        return hip().dot_interaction_bag_fp8_arena(dense, emb_q, emb_scale, ids.arena, int(id_col0), hot, modulo_f,
+                                                   offset_f, int(out_cols))
+    ids, wts = _bag_inputs(ids, wts, T, hot, id_col0)
+    if dense.is_cuda:
+        return hip().dot_interaction_bag_fp8(dense, emb_q, emb_scale, _rows(ids), None if wts is None else _rows(wts),
+                                             hot, modulo_f, offset_f, int(out_cols))
+    rows = _hash_rows(ids, 0, modulo_f.repeat_interleave(hot), offset_f.repeat_interleave(hot))
+    tables = torch.arange(T).repeat_interleave(hot).view(1, -1).expand_as(rows)
+    vals = dequant_table_fp8(emb_q, emb_scale, rows.clamp(0, emb_q.shape[0] - 1), tables)
+    return dot_interaction(dense, _bag_pool_cpu(vals, wts, T, hot, dense.dtype), out_cols)
 
 
 def embedding_bag_fp8(emb_q: torch.Tensor, emb_scale: torch.Tensor, indices: torch.Tensor, offsets: torch.Tensor,
