@@ -1754,6 +1754,65 @@ std::vector<torch::Tensor> cross_mix(torch::Tensor x0, torch::Tensor xl, torch::
   return {z, logit};
 }
 
+// DIN target attention in one launch (din_attention.hip): ids / wts
+// [B, P + 1 + H] row views, table bf16 [V, 64], wpack / fpack:
+// ops.din_attention_pack of an (a1, a2) attention unit -> x bf16 [B, (P + 2) 64]
+// (`out`: a row view that receives it). Limits raise ValueError.
+torch::Tensor din_attention(torch::Tensor table, torch::Tensor ids, torch::Tensor wts, int64_t P, int64_t H,
+                            torch::Tensor wpack, torch::Tensor fpack, int64_t a1, int64_t a2,
+                            c10::optional<torch::Tensor> out) {
+  check_gpu(table, "table");
+  for (auto* t : {&ids, &wts, &wpack, &fpack}) {
+    check_gpu(*t, "din_attention operand");
+    check_same_dev(table, *t, "din_attention operand");
+  }
+  TORCH_CHECK_VALUE(table.dim() == 2 && table.size(1) == 64, "din_attention needs D = 64, got a table of ",
+                    table.sizes());
+  TORCH_CHECK_VALUE(H >= 1 && H <= 64, "din_attention covers 1 <= H <= 64, got H = ", H);
+  TORCH_CHECK_VALUE(a1 >= 1 && a1 <= 128, "din_attention covers 1 <= a1 <= 128, got a1 = ", a1);
+  TORCH_CHECK_VALUE(a2 >= 1 && a2 <= 64, "din_attention covers 1 <= a2 <= 64, got a2 = ", a2);
+  TORCH_CHECK_VALUE(P >= 0, "din_attention needs P >= 0, got P = ", P);
+  TORCH_CHECK(table.scalar_type() == torch::kBFloat16 && table.is_contiguous() && table.size(0) >= 1 &&
+                  table.size(0) < (int64_t(1) << 31),
+              "din_attention: table must be contiguous bf16 [V, 64], 1 <= V < 2^31");
+  const int64_t F = P + 1 + H, B = ids.dim() == 2 ? ids.size(0) : -1;
+  auto cols_ok = [&](const torch::Tensor& t) {
+    return t.dim() == 2 && t.size(0) == B && t.size(1) == F && t.stride(1) == 1 && (B <= 1 || t.stride(0) >= F);
+  };
+  TORCH_CHECK((ids.scalar_type() == torch::kInt64 || ids.scalar_type() == torch::kInt32) && cols_ok(ids),
+              "din_attention: ids must be int32/int64 [B, P + 1 + H] rows with unit inner stride");
+  TORCH_CHECK(wts.scalar_type() == torch::kFloat32 && cols_ok(wts),
+              "din_attention: wts must be fp32 [B, P + 1 + H] rows with unit inner stride");
+  TORCH_CHECK(B < (int64_t(1) << 30), "din_attention: row count");
+  const int64_t a1p = (a1 + 31) / 32 * 32, a2p = (a2 + 15) / 16 * 16, cols = (P + 2) * 64;
+  TORCH_CHECK(wpack.scalar_type() == torch::kBFloat16 && wpack.is_contiguous() &&
+                  wpack.numel() == a1p * 192 + a2p * a1p && fpack.scalar_type() == torch::kFloat32 &&
+                  fpack.is_contiguous() && fpack.numel() == 2 * a1p + 3 * a2p + 1,
+              "din_attention: packed weights do not match a1 = ", a1, ", a2 = ", a2, " (din_attention_pack)");
+  c10::DeviceGuard g(table.device());
+  torch::Tensor x;
+  if (out) {
+    check_gpu(*out, "out");
+    check_same_dev(table, *out, "out");
+    TORCH_CHECK(out->scalar_type() == torch::kBFloat16 && out->dim() == 2 && out->size(0) == B && out->size(1) == cols &&
+                    out->stride(1) == 1,
+                "din_attention: out must be bf16 [B, (P + 2) 64] rows with unit inner stride");
+    TORCH_CHECK_VALUE((B <= 1 || (out->stride(0) >= cols && out->stride(0) % 8 == 0)) &&
+                          reinterpret_cast<uintptr_t>(out->data_ptr()) % 16 == 0,
+                      "din_attention: out needs a leading dimension that is a multiple of 8 and 16-byte alignment");
+    x = *out;
+  } else {
+    x = torch::empty({B, cols}, table.options());
+  }
+  auto ld = [&](const torch::Tensor& t, int64_t n) { return B <= 1 ? n : t.stride(0); };
+  check_hip(dtfs::launch_din_attention(table.data_ptr(), table.size(0), ids.data_ptr(),
+                                       ids.scalar_type() == torch::kInt64, ld(ids, F), wts.data_ptr<float>(),
+                                       ld(wts, F), int(B), int(P), int(H), int(a1p), int(a2p), wpack.data_ptr(),
+                                       fpack.data_ptr<float>(), x.data_ptr(), ld(x, cols), cur_stream(table)),
+            "din_attention");
+  return x;
+}
+
 // The same tail on the block-scaled fp8 matrix cores (mlp_tail_fp8.hip): the
 // kernel MX-quantises X and h2 itself. W2p / W3p: e4m3 weights in the 16x16x128
 // fragment order (ops.pack_bfrag_fp8); sw2 / sw3: per-output-channel scales.
@@ -2640,6 +2699,9 @@ PYBIND11_MODULE(_hip, m) {
   m.def("mlp_tail", &mlp_tail, py::arg("X"), py::arg("W2p"), py::arg("b2"), py::arg("act2"), py::arg("W3p"),
         py::arg("b3"), py::arg("act3"), py::arg("hw"), py::arg("hbias") = 0.0, py::arg("extra") = py::none(),
         py::arg("sigmoid") = true, py::arg("out") = py::none());
+  m.def("din_attention", &din_attention, py::arg("table"), py::arg("ids"), py::arg("wts"), py::arg("P"), py::arg("H"),
+        py::arg("wpack"), py::arg("fpack"), py::arg("a1"), py::arg("a2"), py::arg("out") = py::none(),
+        "DIN target attention over the history in one launch (din_attention.hip) -> x [B, (P + 2) 64]");
   m.def("cross_mix", &cross_mix, py::arg("x0"), py::arg("xl"), py::arg("Vp"), py::arg("Gp"), py::arg("Cp"),
         py::arg("Up"), py::arg("b"), py::arg("E"), py::arg("r"), py::arg("want_z") = true,
         py::arg("head_w") = py::none(), py::arg("out") = py::none(),

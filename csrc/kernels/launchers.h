@@ -183,6 +183,17 @@ hipError_t launch_cross_mix(const void* x0, int64_t ld0, const void* xl, int64_t
                             const void* Vp, const void* Gp, const void* Cp, const void* Up, const float* bias,
                             const float* hw, void* z, int64_t ldz, float* logit, hipStream_t st);
 
+// DIN target attention over the behaviour history (din_attention.hip): ids /
+// weights [B, P + 1 + H] (row-strided, int32 / int64 ids, fp32 weights; columns
+// 0 .. P-1 profile, P the candidate, then the history) and the shared table
+// [V, 64] -> x [B, (P + 2) 64] = [e_0 | .. | e_{P-1} | q | v], bf16 rows of
+// stride ldo (a multiple of 8, 16-byte aligned). wpack / fpack:
+// ops.din_attention_pack (a1p = a1 rounded up to 32, a2p = a2 rounded up to 16).
+// 1 <= H <= 64, 32 <= a1p <= 128, 16 <= a2p <= 64, P >= 0, V < 2^31.
+hipError_t launch_din_attention(const void* table, int64_t V, const void* ids, bool ids64, int64_t ldi,
+                                const float* wts, int64_t ldw, int B, int P, int H, int a1p, int a2p,
+                                const void* wpack, const float* fpack, void* out, int64_t ldo, hipStream_t st);
+
 // The same tail on the block-scaled fp8 matrix cores (mlp_tail_fp8.hip): x
 // (bf16) and the fp32 h2 are MX-quantised inside the kernel (e4m3 + one E8M0
 // byte per 32 columns), W2p / W3p are e4m3 weights in the fragment order of

@@ -37,7 +37,7 @@ PRESET_DIR = os.path.join(REPO, "configs")
 class ModelConfig:
     """Architecture of one CTR model (random-init weights; see models/)."""
 
-    family: str = "deepfm"            # wdl | deepfm | dcn | dcn_v2 | dlrm
+    family: str = "deepfm"            # wdl | deepfm | dcn | dcn_v2 | dlrm | din
     num_fields: int = 43              # reference FIELD_NUM
     vocab_size: int = 1_000_000       # rows of the shared table (wdl/deepfm/dcn/dcn_v2)
     embed_dim: int = 64
@@ -66,6 +66,10 @@ class ModelConfig:
     # fp8 tables needs embedding_exchange: peer (csrc/kernels/peer_lookup_rows.hip)
     embedding_sharding: str = "auto"
     hot_cache_rows: int = -1
+    # din: the last seq_len fields are the behaviour history (weight 0 = padding), the field before them the
+    # candidate item, the rest profile fields; att_dims = the attention unit's two hidden widths (ops.din_attention)
+    seq_len: int = 16
+    att_dims: Tuple[int, int] = (80, 40)
     param_dtype: str = "bf16"         # storage dtype of embeddings + dense weights
     gemm_dtype: str = "bf16"          # bf16 | fp8 (dcn_v2 towers on CDNA4 fp8 MFMA)
     # bf16 | fp8: the last two MLP layers + head as the MX-fp8 fused tail (ops.mlp_tail_fp8);

@@ -21,6 +21,7 @@ deepfm       sigmoid(FM1 + FM2 + head(MLP(emb)))
 dcn          sigmoid(w_c . cross_v1^L(emb) + head(MLP(emb)))
 dcn_v2       sigmoid(w_c . cross_v2^L(emb) + head(MLP(emb)))  (fp8 towers opt.)
 dlrm         sigmoid(head(topMLP(dot(botMLP(dense), emb_t))))
+din          sigmoid(head(MLP([profile | target | attention(target, history)])))
 ===========  ==========================================================
 """
 from __future__ import annotations
@@ -33,7 +34,7 @@ from torch import nn
 
 from .. import ops
 from ..config import ModelConfig
-from .layers import DTYPES, MLP, CrossMix, Dense, hashed_uniform_rows_, init_uniform_, make_generator, pad8
+from .layers import DTYPES, MLP, CrossMix, Dense, DinAttention, hashed_uniform_rows_, init_uniform_, make_generator, pad8
 
 
 class CTRModel(nn.Module):
@@ -718,7 +719,40 @@ class DLRM(CTRModel):
         return self.interact_and_top(dense_out, emb, out=out)
 
 
-FAMILIES = {c.family: c for c in (WideDeep, DeepFM, DCN, DCNv2, DLRM)}
+class DIN(CTRModel):
+    """Deep Interest Network: a request row is P profile fields, the candidate
+    item and ``seq_len`` = H behaviour-history items (weight 0 = padding), all
+    on one shared table. The attention unit scores every history item against
+    the candidate and pools the history with those scores (ops.din_attention,
+    one launch: no [B, F, D] buffer); the MLP reads [profile | target | pooled]."""
+
+    family = "din"
+
+    def __init__(self, cfg: ModelConfig, device="cpu"):
+        super().__init__(cfg, device)
+        V, D, F, H = cfg.vocab_size, cfg.embed_dim, cfg.num_fields, int(cfg.seq_len)
+        P = F - 1 - H
+        if H < 1 or P < 0:
+            raise ValueError(f"din: num_fields = {F} must be P + 1 + seq_len with P >= 0 and seq_len >= 1, got "
+                             f"seq_len = {H}")
+        if len(cfg.att_dims) != 2:
+            raise ValueError(f"din: att_dims must be (a1, a2), got {tuple(cfg.att_dims)}")
+        self.P, self.H = P, H
+        self.emb = self._embedding_table(V, D)
+        self.att = DinAttention(D, cfg.att_dims, self.dtype, self.device_, self.gen)
+        self.mlp = MLP((P + 2) * D, cfg.mlp_dims, self.dtype, self.device_, self.gen)
+        self.head_w = nn.Parameter(init_uniform_(torch.empty(self.mlp.out_dim, device=self.device_), 0.05, self.gen),
+                                   requires_grad=False)
+        self.head_b = 0.0
+
+    def _forward(self, ids, wts, out=None, resolved=None):
+        if wts is None:
+            wts = torch.ones(ids.shape, dtype=torch.float32, device=ids.device)
+        x = self.att(self.emb, ids, wts.float(), self.P, self.H)
+        return self.mlp.forward_head(x, self.head_w, self.head_b, out=out)
+
+
+FAMILIES = {c.family: c for c in (WideDeep, DeepFM, DCN, DCNv2, DLRM, DIN)}
 
 
 def build_model(cfg: ModelConfig, device="cpu", **kw) -> CTRModel:

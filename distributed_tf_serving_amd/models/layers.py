@@ -204,6 +204,53 @@ class CrossMix(nn.Module):
                              head_w=head_w)
 
 
+class DinAttention(nn.Module):
+    """The DIN attention unit (ops.din_attention) in its folded form: Wq, Wk,
+    Wp [a1, D] (z1 about unit rms on unit-rms inputs: bound 1 / sqrt(3 D)), W2
+    [a2, a1], w3 [a2], biases and PReLU slopes (0.25) fp32."""
+
+    def __init__(self, D: int, att_dims: Sequence[int], dtype, device, gen):
+        super().__init__()
+        a1, a2 = (int(a) for a in att_dims)
+        if a1 < 1 or a2 < 1:
+            raise ValueError(f"att_dims must be two positive widths, got {tuple(att_dims)}")
+        self.D, self.a1, self.a2 = D, a1, a2
+
+        def w(shape, bound, dt=torch.float32):
+            return nn.Parameter(init_uniform_(torch.empty(*shape, device=device), bound, gen).to(dt), requires_grad=False)
+
+        self.Wq, self.Wk, self.Wp = (w((a1, D), 1.0 / math.sqrt(3 * D), dtype) for _ in range(3))
+        self.b1 = w((a1,), 0.01)
+        self.alpha1 = nn.Parameter(torch.full((a1,), 0.25, device=device), requires_grad=False)
+        self.W2 = w((a2, a1), math.sqrt(6.0 / (a1 + a2)), dtype)
+        self.b2 = w((a2,), 0.01)
+        self.alpha2 = nn.Parameter(torch.full((a2,), 0.25, device=device), requires_grad=False)
+        self.w3 = w((a2,), math.sqrt(3.0 / a2))
+        self.b3 = nn.Parameter(torch.zeros(1, device=device), requires_grad=False)
+
+    def raw(self):
+        return (self.Wq, self.Wk, self.Wp, self.b1, self.alpha1, self.W2, self.b2, self.alpha2, self.w3, self.b3)
+
+    def packed(self) -> tuple:
+        """ops.din_attention_pack of the weights, re-packed INTO the same
+        buffers whenever one of them changed (see CrossMix.packed)."""
+        key = tuple((t.data_ptr(), t._version) for t in self.raw())
+        cached = self.__dict__.get("_packed")
+        if cached is None or cached[0] != key:
+            fresh = ops.din_attention_pack(tuple(t.detach() for t in self.raw()))
+            if cached is not None and all(o.shape == n.shape and o.device == n.device
+                                          for o, n in zip(cached[1][:2], fresh[:2])):
+                for o, n in zip(cached[1][:2], fresh[:2]):
+                    o.copy_(n)
+                fresh = cached[1]
+            cached = (key, fresh)
+            self.__dict__["_packed"] = cached
+        return cached[1]
+
+    def forward(self, table: torch.Tensor, ids: torch.Tensor, wts: torch.Tensor, P: int, H: int) -> torch.Tensor:
+        return ops.din_attention(table, ids, wts, P, H, self.packed() if table.is_cuda else self.raw())
+
+
 class MLP(nn.Module):
     def __init__(self, in_dim: int, dims: Sequence[int], dtype, device, gen, fp8: bool = False,
                  last_act: str = "relu", in_pad: Optional[int] = None, tail_fp8: bool = False):

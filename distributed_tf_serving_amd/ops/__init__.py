@@ -16,7 +16,8 @@ Op inventory: K0 ``pack_ids``, K1 ``embed``, K1b
 ``rank_arena``; on fp8 tables K1+K5 ``dot_interaction_gather_fp8`` and K1b
 ``embedding_bag_fp8``; K1b+K5 ``dot_interaction_bag`` / ``dot_interaction_bag_fp8``
 (multi-hot bags pooled inside the interaction); through the peer lookup ``dot_interaction_gather_peer`` /
-``peer_bag`` (bf16 or fp8 stores, by the peer tables' dtype).
+``peer_bag`` (bf16 or fp8 stores, by the peer tables' dtype); ``din_attention``
+(DIN: gather + target attention over the history in one launch).
 """
 from __future__ import annotations
 
@@ -1096,6 +1097,155 @@ def cross_mix(x0: torch.Tensor, xl: torch.Tensor, weights, b: torch.Tensor, want
         out.copy_(zb)
         zb = out
     return (zb if want_z else None), logit
+
+
+# ------------------------------------------------------------------ DIN target attention
+DIN_MAX_H, DIN_MAX_A1, DIN_MAX_A2 = 64, 128, 64  # csrc/kernels/din_attention.hip
+
+
+def din_attention_check(D: int, P: int, H: int, a1: int, a2: int) -> None:
+    """The range csrc/kernels/din_attention.hip covers; ValueError names the limit."""
+    if D != 64:
+        raise ValueError(f"din_attention needs D = 64 on the GPU, got D = {D}")
+    if not 1 <= H <= DIN_MAX_H:
+        raise ValueError(f"din_attention covers 1 <= H <= {DIN_MAX_H}, got H = {H}")
+    if not 1 <= a1 <= DIN_MAX_A1:
+        raise ValueError(f"din_attention covers 1 <= a1 <= {DIN_MAX_A1}, got a1 = {a1}")
+    if not 1 <= a2 <= DIN_MAX_A2:
+        raise ValueError(f"din_attention covers 1 <= a2 <= {DIN_MAX_A2}, got a2 = {a2}")
+    if P < 0:
+        raise ValueError(f"din_attention needs P >= 0, got P = {P}")
+
+
+def din_attention_fits(D: int, P: int, H: int, a1: int, a2: int) -> bool:
+    """Shapes the fused attention kernel serves."""
+    try:
+        din_attention_check(D, P, H, a1, a2)
+    except ValueError:
+        return False
+    return True
+
+
+def din_fold(W1: torch.Tensor):
+    """The paper's first attention layer W1 = [A | B | C | E] [a1, 4 D] on
+    u = [q, k, q - k, q * k] -> the folded (Wq, Wk, Wp) = (A + C, B - C, E),
+    folded in fp32 and then rounded to bf16."""
+    a1, D4 = W1.shape
+    if D4 % 4:
+        raise ValueError(f"din_fold needs W1 [a1, 4 D], got {tuple(W1.shape)}")
+    A, Bk, C, E = W1.float().view(a1, 4, D4 // 4).unbind(1)
+    return (A + C).to(torch.bfloat16), (Bk - C).to(torch.bfloat16), E.contiguous().to(torch.bfloat16)
+
+
+def _din_dims(weights):
+    Wq, Wk, Wp, b1, al1, W2, b2, al2, w3, b3 = weights
+    a1, D = (int(s) for s in Wq.shape)
+    a2 = int(W2.shape[0])
+    if (tuple(Wk.shape) != (a1, D) or tuple(Wp.shape) != (a1, D) or tuple(W2.shape) != (a2, a1) or b1.numel() != a1
+            or al1.numel() != a1 or b2.numel() != a2 or al2.numel() != a2 or w3.numel() != a2 or b3.numel() != 1):
+        raise ValueError("din_attention weights: Wq, Wk, Wp [a1, D], b1, alpha1 [a1], W2 [a2, a1], b2, alpha2, w3 "
+                         f"[a2], b3 [1]; got {[tuple(t.shape) for t in weights]}")
+    return D, a1, a2
+
+
+def _din_frag(W: torch.Tensor) -> torch.Tensor:
+    """:func:`pack_bfrag` order for K % 32 == 0: fragment (n16, k32) is 64
+    lanes x 8 values, lane (fr, fq) holding W[16 n16 + fr, 32 k32 + 8 fq + e]."""
+    N, K = W.shape
+    return W.reshape(N // 16, 16, K // 32, 4, 8).permute(0, 2, 3, 1, 4).reshape(-1)
+
+
+def din_attention_pack(weights) -> tuple:
+    """The attention unit's weights (Wq, Wk, Wp, b1, alpha1, W2, b2, alpha2, w3,
+    b3) as csrc/kernels/din_attention.hip reads them -> (wpack bf16, fpack fp32,
+    a1, a2). a1 is zero padded to a1p (a multiple of 32), a2 to a2p (a multiple
+    of 16). wpack: [Wk | Wp] [a1p, 128], Wq [a1p, 64] and W2 [a2p, a1p] in MFMA
+    fragment order, back to back; the a1 units are permuted inside every group
+    of 32 (block t, row 4 j + s = unit 8 j + 4 t + s: a lane's outputs of a
+    block pair are then 8 consecutive units, layer 2's A fragment). fpack: b1,
+    alpha1 (permuted alike), b2, alpha2, w3, b3."""
+    Wq, Wk, Wp, b1, al1, W2, b2, al2, w3, b3 = weights
+    D, a1, a2 = _din_dims(weights)
+    din_attention_check(D, 0, 1, a1, a2)
+    a1p, a2p = -(-a1 // 32) * 32, -(-a2 // 16) * 16
+    dev = Wq.device
+
+    def rows(t, n, dtype):  # zero padded to n rows
+        z = torch.zeros(n, *t.shape[1:], dtype=dtype, device=dev)
+        z[:t.shape[0]] = t.to(dtype)
+        return z
+
+    def perm(t):  # the unit permutation, on dim 0
+        return t.reshape(a1p // 32, 4, 2, 4, *t.shape[1:]).transpose(1, 2).reshape(t.shape)
+
+    bf, f32 = torch.bfloat16, torch.float32
+    W1m = perm(rows(torch.cat([Wk, Wp], dim=1), a1p, bf))
+    Wqz = perm(rows(Wq, a1p, bf))
+    W2z = torch.zeros(a2p, a1p, dtype=bf, device=dev)
+    W2z[:a2, :a1] = W2
+    wpack = torch.cat([_din_frag(W1m), _din_frag(Wqz), _din_frag(W2z)]).contiguous()
+    fpack = torch.cat([perm(rows(b1.reshape(-1), a1p, f32)), perm(rows(al1.reshape(-1), a1p, f32)),
+                       rows(b2.reshape(-1), a2p, f32), rows(al2.reshape(-1), a2p, f32),
+                       rows(w3.reshape(-1), a2p, f32), b3.reshape(1).to(f32)]).contiguous()
+    return wpack, fpack, a1, a2
+
+
+def din_attention(table: torch.Tensor, ids: torch.Tensor, wts: torch.Tensor, P: int, H: int, weights,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Deep Interest Network target attention (Zhou et al. 2018), one launch on
+    the GPU (csrc/kernels/din_attention.hip). ``ids`` / ``wts`` [B, P + 1 + H]:
+    columns 0 .. P-1 profile fields, column P the candidate, then the history
+    (weight 0 = padding); one shared ``table`` [V, D], rows ``id mod V``:
+
+        e_f  = bf16(fp32(w_f) * row(id_f mod V))        q = e_P, k_h = e_{P+1+h}
+        p_h  = bf16(q * k_h)
+        a1_h = bf16(prelu(Wq q + Wk k_h + Wp p_h + b1, alpha1))
+        a2_h = prelu(W2 a1_h + b2, alpha2)               s_h = w3 . a2_h + b3
+        v    = bf16(sum_h s_h k_h)
+        x    = [e_0 | .. | e_{P-1} | q | v]              [B, (P + 2) D]
+
+    Every product and sum is fp32; the roundings are the ones written (e, p,
+    a1, v). No softmax, as in the paper. ``weights``: the raw 10-tuple (Wq, Wk,
+    Wp bf16 [a1, D], b1, alpha1 fp32 [a1], W2 bf16 [a2, a1], b2, alpha2, w3
+    fp32 [a2], b3 fp32 [1]; :func:`din_fold` makes the first three from the
+    paper's 4-block layer) or, on the GPU, :func:`din_attention_pack` of it.
+    ``out``: a bf16 [B, (P + 2) D] row view that receives x. CPU: the same
+    contract in plain fp32 ops, any D."""
+    P, H = int(P), int(H)
+    raw = len(weights) == 10
+    if table.is_cuda:
+        if raw:
+            D, a1, a2 = _din_dims(weights)
+        else:
+            D, a1, a2 = int(table.shape[1]), int(weights[2]), int(weights[3])
+        din_attention_check(int(table.shape[1]), P, H, a1, a2)
+        if D != 64:
+            raise ValueError(f"din_attention needs D = 64 on the GPU, got weights of D = {D}")
+        wpack, fpack = (din_attention_pack(weights) if raw else weights)[:2]
+        return hip().din_attention(table, _rows(ids), _rows(wts), P, H, wpack, fpack, a1, a2, out)
+    if not raw:
+        raise ValueError("din_attention on the CPU takes the raw 10-tuple of weights")
+    Wq, Wk, Wp, b1, al1, W2, b2, al2, w3, b3 = (t.float() for t in weights)
+    _din_dims(weights)
+    if H < 1 or P < 0 or ids.shape[1] != P + 1 + H:
+        raise ValueError(f"din_attention: {ids.shape[1]} columns != P + 1 + H = {P} + 1 + {H} (H >= 1, P >= 0)")
+    dt = table.dtype
+    prelu = lambda z, a: torch.where(z > 0, z, a * z)  # noqa: E731
+    e = (table[torch.remainder(ids.long(), table.shape[0])].float() * wts.float().unsqueeze(-1)).to(dt)  # [B, F, D]
+    q, k = e[:, P].float(), e[:, P + 1:].float()
+    p = (q.unsqueeze(1) * k).to(dt).float()
+    z1 = (q @ Wq.t() + b1.view(1, -1)).unsqueeze(1) + k @ Wk.t() + p @ Wp.t()
+    a1v = prelu(z1, al1.view(1, 1, -1)).to(dt).float()
+    a2v = prelu(a1v @ W2.t() + b2.view(1, 1, -1), al2.view(1, 1, -1))
+    s = a2v @ w3.view(-1) + b3.view(())
+    v = torch.zeros_like(q)
+    for h in range(H):  # h ascending: a padding entry adds an exact zero
+        v += s[:, h:h + 1] * k[:, h]
+    x = torch.cat([e[:, :P + 1].reshape(e.shape[0], -1), v.to(dt)], dim=1)
+    if out is not None:
+        out.copy_(x)
+        return out
+    return x
 
 
 def unpack_bfrag(Wp: torch.Tensor, N: int, K: int) -> torch.Tensor:
