@@ -1813,6 +1813,76 @@ torch::Tensor din_attention(torch::Tensor table, torch::Tensor ids, torch::Tenso
   return x;
 }
 
+// One xDeepFM CIN layer in one launch (cin.hip). x0 bf16 [B, F, 64], xp bf16
+// [B, >= H_prev, 64] (candidate-strided views), Wp: ops.cin_pack of W [H,
+// H_prev, F]. Returns {xk [B, H_pad, 64] (undefined without want_x; `out`
+// receives it), logit fp32 [B]}; a given `logit` is added to. Limits raise
+// ValueError.
+std::vector<torch::Tensor> cin_layer(torch::Tensor x0, torch::Tensor xp, torch::Tensor Wp, int64_t H, int64_t H_prev,
+                                     torch::Tensor bias, torch::Tensor w_out, bool want_x,
+                                     c10::optional<torch::Tensor> logit, c10::optional<torch::Tensor> out) {
+  check_gpu(x0, "x0");
+  check_gpu(xp, "xp");
+  check_same_dev(x0, xp, "xp");
+  for (auto* t : {&Wp, &bias, &w_out}) {
+    check_dev(*t, "cin_layer operand");
+    check_same_dev(x0, *t, "cin_layer operand");
+  }
+  TORCH_CHECK(x0.dim() == 3 && xp.dim() == 3, "cin_layer: x0 [B, F, D] and xp [B, H_prev, D]");
+  const int64_t B = x0.size(0), F = x0.size(1);
+  TORCH_CHECK_VALUE(x0.size(2) == 64, "cin_layer needs D = 64 on the GPU, got D = ", x0.size(2));
+  TORCH_CHECK_VALUE(F >= 1 && F <= 64, "cin_layer covers 1 <= F <= 64, got F = ", F);
+  TORCH_CHECK_VALUE(H_prev >= 1 && H_prev <= 256, "cin_layer covers 1 <= H_prev <= 256, got H_prev = ", H_prev);
+  TORCH_CHECK_VALUE(H >= 1 && H <= 256, "cin_layer covers 1 <= H <= 256, got H = ", H);
+  auto maps_ok = [&](const torch::Tensor& t, int64_t n) {
+    return t.scalar_type() == torch::kBFloat16 && t.dim() == 3 && t.size(0) == B && t.size(1) >= n &&
+           t.size(2) == 64 && t.stride(2) == 1 && (t.size(1) == 1 || t.stride(1) == 64) &&
+           (B <= 1 || (t.stride(0) >= t.size(1) * 64 && t.stride(0) % 8 == 0)) &&
+           reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+  };
+  TORCH_CHECK(maps_ok(x0, F) && maps_ok(xp, H_prev),
+              "cin_layer: x0 [B, F, 64], xp [B, >= H_prev, 64] must be bf16 with contiguous maps, a candidate stride "
+              "that is a multiple of 8 and 16-byte alignment");
+  TORCH_CHECK(B < (int64_t(1) << 31), "cin_layer: row count");
+  const int64_t HPAD = (H + 15) / 16 * 16;
+  const int64_t nw = int64_t(dtfs::cin_passes(int(H))) * dtfs::cin_pass_blocks(int(H)) * 16 * ((H_prev + 3) / 4 * 4) *
+                     ((F + 7) / 8 * 8);
+  TORCH_CHECK(Wp.scalar_type() == torch::kBFloat16 && Wp.is_contiguous() && Wp.numel() == nw,
+              "cin_layer: packed weights do not match H = ", H, ", H_prev = ", H_prev, ", F = ", F, " (cin_pack)");
+  for (auto* t : {&bias, &w_out})
+    TORCH_CHECK(t->scalar_type() == torch::kFloat32 && t->is_contiguous() && t->numel() == H,
+                "cin_layer: bias, w_out must be fp32 [H]");
+  c10::DeviceGuard g(x0.device());
+  torch::Tensor xk, lg;
+  if (want_x) {
+    if (out) {
+      check_gpu(*out, "out");
+      check_same_dev(x0, *out, "out");
+      TORCH_CHECK(maps_ok(*out, HPAD) && out->size(1) == HPAD, "cin_layer: out must be bf16 [B, H_pad, 64] maps like xp");
+      xk = *out;
+    } else {
+      xk = torch::empty({B, HPAD, 64}, x0.options());
+    }
+  }
+  if (logit) {
+    check_gpu(*logit, "logit");
+    check_same_dev(x0, *logit, "logit");
+    TORCH_CHECK(logit->scalar_type() == torch::kFloat32 && logit->dim() == 1 && logit->size(0) == B &&
+                    logit->is_contiguous(),
+                "cin_layer: logit must be contiguous fp32 [B]");
+    lg = *logit;
+  } else {
+    lg = torch::empty({B}, x0.options().dtype(torch::kFloat32));
+  }
+  auto ld = [&](const torch::Tensor& t) { return B <= 1 ? t.size(1) * 64 : t.stride(0); };
+  check_hip(dtfs::launch_cin_layer(x0.data_ptr(), ld(x0), xp.data_ptr(), ld(xp), int(B), int(F), int(H_prev), int(H),
+                                   Wp.data_ptr(), bias.data_ptr<float>(), w_out.data_ptr<float>(),
+                                   want_x ? xk.data_ptr() : nullptr, want_x ? ld(xk) : 0, lg.data_ptr<float>(),
+                                   logit.has_value(), cur_stream(x0)),
+            "cin_layer");
+  return {xk, lg};
+}
+
 // The same tail on the block-scaled fp8 matrix cores (mlp_tail_fp8.hip): the
 // kernel MX-quantises X and h2 itself. W2p / W3p: e4m3 weights in the 16x16x128
 // fragment order (ops.pack_bfrag_fp8); sw2 / sw3: per-output-channel scales.
@@ -2706,6 +2776,9 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("Up"), py::arg("b"), py::arg("E"), py::arg("r"), py::arg("want_z") = true,
         py::arg("head_w") = py::none(), py::arg("out") = py::none(),
         "DCN-v2 mixture-of-low-rank-experts cross layer in one launch (cross_mix.hip) -> [z, logit]");
+  m.def("cin_layer", &cin_layer, py::arg("x0"), py::arg("xp"), py::arg("Wp"), py::arg("H"), py::arg("H_prev"),
+        py::arg("bias"), py::arg("w_out"), py::arg("want_x") = true, py::arg("logit") = py::none(),
+        py::arg("out") = py::none(), "xDeepFM CIN layer in one launch (cin.hip) -> [xk, logit]");
   m.def("mlp_tail_fp8", &mlp_tail_fp8, py::arg("X"), py::arg("W2p"), py::arg("sw2"), py::arg("b2"), py::arg("act2"),
         py::arg("W3p"), py::arg("sw3"), py::arg("b3"), py::arg("act3"), py::arg("hw"), py::arg("hbias") = 0.0,
         py::arg("extra") = py::none(), py::arg("sigmoid") = true, py::arg("out") = py::none(),

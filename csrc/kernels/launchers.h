@@ -194,6 +194,21 @@ hipError_t launch_din_attention(const void* table, int64_t V, const void* ids, b
                                 const float* wts, int64_t ldw, int B, int P, int H, int a1p, int a2p,
                                 const void* wpack, const float* fpack, void* out, int64_t ldo, hipStream_t st);
 
+// One xDeepFM CIN layer per launch (cin.hip):
+// X^k[b,h,d] = bf16(bias[h] + sum_{i,j} W[h,i,j] bf16(xp[b,i,d] x0[b,j,d])),
+// logit[b] (+)= sum_h w_out[h] sum_d float(X^k[b,h,d]). x0 [B, F, 64] and xp
+// [B, >= H_prev, 64]: bf16, maps contiguous, candidate strides ld0 / ldp in
+// elements (multiples of 8), 16-byte aligned. xk [B, H_pad, 64] (H_pad = H
+// rounded up to 16; maps >= H are written as zeros) may be null. Wp:
+// ops.cin_pack ([pass][i / 4][j / 8][column block][64 lanes][8]; cin_passes(H)
+// passes of cin_pass_blocks(H) 16-column blocks). accumulate: logit += instead
+// of =. 1 <= F <= 64, 1 <= H_prev, H <= 256.
+inline int cin_passes(int H) { return ((H + 15) / 16 + 7) / 8; }
+inline int cin_pass_blocks(int H) { return ((H + 15) / 16 + cin_passes(H) - 1) / cin_passes(H); }
+hipError_t launch_cin_layer(const void* x0, int64_t ld0, const void* xp, int64_t ldp, int B, int F, int H_prev, int H,
+                            const void* Wp, const float* bias, const float* w_out, void* xk, int64_t ldk,
+                            float* logit, bool accumulate, hipStream_t st);
+
 // The same tail on the block-scaled fp8 matrix cores (mlp_tail_fp8.hip): x
 // (bf16) and the fp32 h2 are MX-quantised inside the kernel (e4m3 + one E8M0
 // byte per 32 columns), W2p / W3p are e4m3 weights in the fragment order of

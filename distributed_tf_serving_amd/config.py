@@ -37,7 +37,7 @@ PRESET_DIR = os.path.join(REPO, "configs")
 class ModelConfig:
     """Architecture of one CTR model (random-init weights; see models/)."""
 
-    family: str = "deepfm"            # wdl | deepfm | dcn | dcn_v2 | dlrm | din
+    family: str = "deepfm"            # wdl | deepfm | dcn | dcn_v2 | dlrm | din | xdeepfm
     num_fields: int = 43              # reference FIELD_NUM
     vocab_size: int = 1_000_000       # rows of the shared table (wdl/deepfm/dcn/dcn_v2)
     embed_dim: int = 64
@@ -70,6 +70,8 @@ class ModelConfig:
     # candidate item, the rest profile fields; att_dims = the attention unit's two hidden widths (ops.din_attention)
     seq_len: int = 16
     att_dims: Tuple[int, int] = (80, 40)
+    # xdeepfm: feature maps per CIN layer (ops.cin_layer; each <= 256, num_fields <= 64, embed_dim 64 on the GPU)
+    cin_dims: Tuple[int, ...] = (128, 128)
     param_dtype: str = "bf16"         # storage dtype of embeddings + dense weights
     gemm_dtype: str = "bf16"          # bf16 | fp8 (dcn_v2 towers on CDNA4 fp8 MFMA)
     # bf16 | fp8: the last two MLP layers + head as the MX-fp8 fused tail (ops.mlp_tail_fp8);

@@ -251,6 +251,58 @@ class DinAttention(nn.Module):
         return ops.din_attention(table, ids, wts, P, H, self.packed() if table.is_cuda else self.raw())
 
 
+class CIN(nn.Module):
+    """xDeepFM's Compressed Interaction Network: layer k holds W [H_k, H_{k-1},
+    F] bf16 (H_0 = F), bias and the output weights w_out fp32 [H_k]
+    (ops.cin_layer). ``x_rms``: the rms of X^0's elements; W is drawn so that
+    every X^k keeps about that rms (std 1 / (x_rms sqrt(H_{k-1} F))), and w_out
+    so that a layer's logit has about unit-order spread (p^k[b, h] is a sum of
+    D elements: std 1 / (x_rms sqrt(D H_k L)))."""
+
+    def __init__(self, F: int, D: int, dims: Sequence[int], x_rms: float, dtype, device, gen):
+        super().__init__()
+        dims = [int(h) for h in dims]
+        if not dims or min(dims) < 1:
+            raise ValueError(f"cin_dims must be one or more positive widths, got {tuple(dims)}")
+        self.F, self.D, self.dims = F, D, dims
+        Ws, bs, os_ = [], [], []
+        hp = F
+        for h in dims:
+            bw = math.sqrt(3.0) / (x_rms * math.sqrt(hp * F))
+            Ws.append(nn.Parameter(init_uniform_(torch.empty(h, hp, F, device=device), bw, gen).to(dtype),
+                                   requires_grad=False))
+            bs.append(nn.Parameter(init_uniform_(torch.empty(h, device=device), 0.01 * x_rms, gen), requires_grad=False))
+            bo = math.sqrt(3.0) / (x_rms * math.sqrt(D * h * len(dims)))
+            os_.append(nn.Parameter(init_uniform_(torch.empty(h, device=device), bo, gen), requires_grad=False))
+            hp = h
+        self.W, self.bias, self.w_out = nn.ParameterList(Ws), nn.ParameterList(bs), nn.ParameterList(os_)
+
+    def packed(self) -> list:
+        """ops.cin_pack of every layer's W, re-packed INTO the same buffers
+        whenever a weight changed (see CrossMix.packed)."""
+        key = tuple((t.data_ptr(), t._version) for t in self.W)
+        cached = self.__dict__.get("_packed")
+        if cached is None or cached[0] != key:
+            fresh = [ops.cin_pack(t.detach()) for t in self.W]
+            if cached is not None and all(o[0].shape == n[0].shape and o[0].device == n[0].device
+                                          for o, n in zip(cached[1], fresh)):
+                for o, n in zip(cached[1], fresh):
+                    o[0].copy_(n[0])
+                fresh = cached[1]
+            cached = (key, fresh)
+            self.__dict__["_packed"] = cached
+        return cached[1]
+
+    def forward(self, x0: torch.Tensor) -> torch.Tensor:
+        """x0 [B, F, D] (a view) -> the CIN logit fp32 [B]; the last layer
+        writes no feature maps."""
+        ws = self.packed() if x0.is_cuda else list(self.W)
+        xp, logit, last = x0, None, len(self.dims) - 1
+        for k, w in enumerate(ws):
+            xp, logit = ops.cin_layer(x0, xp, w, self.bias[k], self.w_out[k], want_x=k < last, logit=logit)
+        return logit
+
+
 class MLP(nn.Module):
     def __init__(self, in_dim: int, dims: Sequence[int], dtype, device, gen, fp8: bool = False,
                  last_act: str = "relu", in_pad: Optional[int] = None, tail_fp8: bool = False):

@@ -17,7 +17,8 @@ Op inventory: K0 ``pack_ids``, K1 ``embed``, K1b
 ``embedding_bag_fp8``; K1b+K5 ``dot_interaction_bag`` / ``dot_interaction_bag_fp8``
 (multi-hot bags pooled inside the interaction); through the peer lookup ``dot_interaction_gather_peer`` /
 ``peer_bag`` (bf16 or fp8 stores, by the peer tables' dtype); ``din_attention``
-(DIN: gather + target attention over the history in one launch).
+(DIN: gather + target attention over the history in one launch); ``cin_layer``
+(xDeepFM: one CIN layer per launch, the outer product formed in registers).
 """
 from __future__ import annotations
 
@@ -1246,6 +1247,103 @@ def din_attention(table: torch.Tensor, ids: torch.Tensor, wts: torch.Tensor, P: 
         out.copy_(x)
         return out
     return x
+
+
+# ------------------------------------------------------------------ xDeepFM CIN
+CIN_MAX_F, CIN_MAX_H = 64, 256  # csrc/kernels/cin.hip
+
+
+def cin_check(D: int, F: int, H_prev: int, H: int) -> None:
+    """The range csrc/kernels/cin.hip covers; ValueError names the limit."""
+    if D != 64:
+        raise ValueError(f"cin_layer needs D = 64 on the GPU, got D = {D}")
+    if not 1 <= F <= CIN_MAX_F:
+        raise ValueError(f"cin_layer covers 1 <= F <= {CIN_MAX_F}, got F = {F}")
+    if not 1 <= H_prev <= CIN_MAX_H:
+        raise ValueError(f"cin_layer covers 1 <= H_prev <= {CIN_MAX_H}, got H_prev = {H_prev}")
+    if not 1 <= H <= CIN_MAX_H:
+        raise ValueError(f"cin_layer covers 1 <= H <= {CIN_MAX_H}, got H = {H}")
+
+
+def cin_split(H: int) -> Tuple[int, int]:
+    """(column passes, 16-column blocks per pass) of csrc/kernels/cin.hip: at
+    most 8 blocks (128 accumulator registers) per pass."""
+    nc = -(-H // 16)
+    passes = -(-nc // 8)
+    return passes, -(-nc // passes)
+
+
+def cin_pack(W: torch.Tensor) -> tuple:
+    """CIN weights W [H, H_prev, F] bf16 as csrc/kernels/cin.hip streams them
+    -> (Wp, H, H_prev, F). i is zero padded to a multiple of 4, j to a multiple
+    of 8, h to passes x blocks x 16 (:func:`cin_split`). One 32-deep K step is
+    4 values of i times one 8-wide block of j; steps run i-major. Wp is
+    [pass][i / 4][j / 8][block] fragments of 64 lanes x 8 values, lane (fr, fq)
+    holding W[16 (pass blocks + block) + fr, 4 (i / 4) + fq, 8 (j / 8) .. + 7]
+    (:func:`pack_bfrag` order: 1 KiB contiguous per fragment)."""
+    if W.dim() != 3:
+        raise ValueError(f"cin_pack takes W [H, H_prev, F], got {tuple(W.shape)}")
+    H, Hp, F = (int(s) for s in W.shape)
+    cin_check(64, F, Hp, H)
+    P, NCP = cin_split(H)
+    IT, JB = -(-Hp // 4), -(-F // 8)
+    Wz = torch.zeros(P * NCP * 16, IT * 4, JB * 8, dtype=torch.bfloat16, device=W.device)
+    Wz[:H, :Hp, :F] = W
+    # (p, nc, fr, t, fq, jb, s) -> (p, t, jb, nc, fq, fr, s)
+    Wp = Wz.reshape(P, NCP, 16, IT, 4, JB, 8).permute(0, 3, 5, 1, 4, 2, 6).contiguous()
+    return Wp, H, Hp, F
+
+
+def cin_layer(x0: torch.Tensor, xp: torch.Tensor, weights, bias: torch.Tensor, w_out: torch.Tensor,
+              want_x: bool = True, logit: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
+    """One Compressed Interaction Network layer of xDeepFM (Lian et al. 2018),
+    one launch on the GPU (csrc/kernels/cin.hip; the [B, H_prev, F, D] outer
+    product never exists in memory):
+
+        X^k[b,h,d] = bias[h] + sum_{i < H_prev} sum_{j < F} W[h,i,j] xp[b,i,d] x0[b,j,d]
+        p^k[b,h]   = sum_d X^k[b,h,d]          logit[b] (+)= sum_h w_out[h] p^k[b,h]
+
+    ``x0`` bf16 [B, F, D] (the embed output viewed in place), ``xp`` bf16
+    [B, >= H_prev, D] (layer 1: x0 itself; later: the previous layer's xk),
+    both candidate-strided views. ``weights``: W [H, H_prev, F] bf16 or, on the
+    GPU, :func:`cin_pack` of it. ``bias``, ``w_out`` fp32 [H]. Returns (xk or
+    None, logit): xk bf16 [B, H_pad, D], H_pad = H rounded up to 16 and maps
+    h >= H exact zeros (``out`` receives it); logit fp32 [B]. A given ``logit``
+    is accumulated into (one writer per candidate, no atomics).
+
+    Rounding: Z = bf16(float(xp) * float(x0)); the sum over (i, j) and the bias
+    are fp32; X^k = bf16(.); p^k sums float(X^k) of the rounded values in fp32,
+    so the logit is the same whether or not xk is written. GPU: D = 64,
+    F <= 64, H_prev, H <= 256 (:func:`cin_check`). CPU: the same contract as
+    an fp32 einsum, any D, chunked over B."""
+    raw = isinstance(weights, torch.Tensor)
+    B, F, D = (int(s) for s in x0.shape)
+    H, Hp = (int(weights.shape[0]), int(weights.shape[1])) if raw else (int(weights[1]), int(weights[2]))
+    Fw = int(weights.shape[2]) if raw else int(weights[3])
+    if Fw != F or xp.dim() != 3 or xp.shape[0] != B or xp.shape[1] < Hp or xp.shape[2] != D:
+        raise ValueError(f"cin_layer: W [H, H_prev, F] = [{H}, {Hp}, {Fw}] does not match x0 {tuple(x0.shape)}, "
+                         f"xp {tuple(xp.shape)}")
+    if x0.is_cuda:
+        cin_check(D, F, Hp, H)
+        Wp = cin_pack(weights)[0] if raw else weights[0]
+        xk, lg = hip().cin_layer(x0, xp, Wp, H, Hp, bias, w_out, want_x, logit, out)
+        return (xk if want_x else None), lg
+    if not raw:
+        raise ValueError("cin_layer on the CPU takes the raw W [H, H_prev, F]")
+    HPAD = -(-H // 16) * 16
+    Wf, step = weights.float(), max(1, (1 << 22) // max(1, Hp * F * D))
+    xk = torch.zeros(B, HPAD, D, dtype=x0.dtype) if out is None or not want_x else out
+    lg = torch.empty(B, dtype=torch.float32)
+    for s in range(0, B, step):
+        z = (xp[s:s + step, :Hp].float().unsqueeze(2) * x0[s:s + step].float().unsqueeze(1)).to(x0.dtype).float()
+        x = (torch.einsum("bijd,hij->bhd", z, Wf) + bias.float().view(1, -1, 1)).to(x0.dtype)
+        lg[s:s + step] = x.float().sum(dim=2) @ w_out.float()
+        xk[s:s + step, :H] = x
+        xk[s:s + step, H:] = 0
+    if logit is not None:
+        logit += lg
+        lg = logit
+    return (xk if want_x else None), lg
 
 
 def unpack_bfrag(Wp: torch.Tensor, N: int, K: int) -> torch.Tensor:
