@@ -1883,6 +1883,74 @@ std::vector<torch::Tensor> cin_layer(torch::Tensor x0, torch::Tensor xp, torch::
   return {xk, lg};
 }
 
+// A stack of L AutoInt interacting layers in one launch (autoint.hip). x bf16
+// [B, F, 64] (a strided view), wpack / opack: ops.autoint_pack. Returns {y^L
+// [B, F, 64] (undefined without want_x; `out` receives it), logit fp32 [B]
+// (undefined without opack)}; a given `logit` is added to. Limits raise
+// ValueError.
+std::vector<torch::Tensor> autoint(torch::Tensor x, torch::Tensor wpack, c10::optional<torch::Tensor> opack,
+                                   int64_t heads, int64_t L, bool want_x, c10::optional<torch::Tensor> logit,
+                                   c10::optional<torch::Tensor> out) {
+  check_gpu(x, "x");
+  check_dev(wpack, "autoint weights");
+  check_same_dev(x, wpack, "autoint weights");
+  TORCH_CHECK(x.dim() == 3 && x.scalar_type() == torch::kBFloat16, "autoint: x must be bf16 [B, F, D]");
+  const int64_t B = x.size(0), F = x.size(1);
+  TORCH_CHECK_VALUE(x.size(2) == 64, "autoint needs D = 64 on the GPU, got D = ", x.size(2));
+  TORCH_CHECK_VALUE(F >= 1 && F <= 64, "autoint covers 1 <= F <= 64, got F = ", F);
+  TORCH_CHECK_VALUE(heads == 1 || heads == 2 || heads == 4, "autoint covers heads in {1, 2, 4}, got heads = ", heads);
+  TORCH_CHECK_VALUE(L >= 1 && L <= 4, "autoint covers 1 <= L <= 4, got L = ", L);
+  auto rows_ok = [&](const torch::Tensor& t) {
+    return t.stride(2) == 1 && (F <= 1 || (t.stride(1) >= 64 && t.stride(1) % 8 == 0)) &&
+           (B <= 1 || t.stride(0) % 8 == 0) && reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+  };
+  TORCH_CHECK_VALUE(rows_ok(x), "autoint needs 16-byte aligned rows: x strides ", x.strides(), " (elements)");
+  TORCH_CHECK(B < (int64_t(1) << 31), "autoint: row count");
+  TORCH_CHECK(wpack.scalar_type() == torch::kBFloat16 && wpack.is_contiguous() && wpack.numel() == L * 4 * 4096,
+              "autoint: packed weights do not match L = ", L, " (autoint_pack)");
+  TORCH_CHECK(want_x || opack, "autoint: nothing to compute (no w_out and want_x = False)");
+  const int64_t nmb = (F + 15) / 16;
+  if (opack) {
+    check_dev(*opack, "autoint w_out");
+    check_same_dev(x, *opack, "autoint w_out");
+    TORCH_CHECK(opack->scalar_type() == torch::kFloat32 && opack->is_contiguous() && opack->numel() == nmb * 1024,
+                "autoint: packed w_out does not match F = ", F, " (autoint_pack)");
+  }
+  c10::DeviceGuard g(x.device());
+  torch::Tensor y, lg;
+  if (want_x) {
+    if (out) {
+      check_gpu(*out, "out");
+      check_same_dev(x, *out, "out");
+      TORCH_CHECK(out->scalar_type() == torch::kBFloat16 && out->sizes() == x.sizes(), "autoint: out must be bf16 like x");
+      TORCH_CHECK_VALUE(rows_ok(*out), "autoint needs 16-byte aligned rows: out strides ", out->strides(), " (elements)");
+      y = *out;
+    } else {
+      y = torch::empty({B, F, 64}, x.options());
+    }
+  }
+  if (opack) {
+    if (logit) {
+      check_gpu(*logit, "logit");
+      check_same_dev(x, *logit, "logit");
+      TORCH_CHECK(logit->scalar_type() == torch::kFloat32 && logit->dim() == 1 && logit->size(0) == B &&
+                      logit->is_contiguous(),
+                  "autoint: logit must be contiguous fp32 [B]");
+      lg = *logit;
+    } else {
+      lg = torch::empty({B}, x.options().dtype(torch::kFloat32));
+    }
+  }
+  auto ldb = [&](const torch::Tensor& t) { return B <= 1 ? F * 64 : t.stride(0); };
+  auto ldr = [&](const torch::Tensor& t) { return F <= 1 ? int64_t(64) : t.stride(1); };
+  check_hip(dtfs::launch_autoint(x.data_ptr(), ldb(x), ldr(x), int(B), int(F), int(heads), int(L), wpack.data_ptr(),
+                                 opack ? opack->data_ptr<float>() : nullptr, want_x ? y.data_ptr() : nullptr,
+                                 want_x ? ldb(y) : 0, want_x ? ldr(y) : 64, opack ? lg.data_ptr<float>() : nullptr,
+                                 opack && logit.has_value(), cur_stream(x)),
+            "autoint");
+  return {y, lg};
+}
+
 // The same tail on the block-scaled fp8 matrix cores (mlp_tail_fp8.hip): the
 // kernel MX-quantises X and h2 itself. W2p / W3p: e4m3 weights in the 16x16x128
 // fragment order (ops.pack_bfrag_fp8); sw2 / sw3: per-output-channel scales.
@@ -2779,6 +2847,9 @@ PYBIND11_MODULE(_hip, m) {
   m.def("cin_layer", &cin_layer, py::arg("x0"), py::arg("xp"), py::arg("Wp"), py::arg("H"), py::arg("H_prev"),
         py::arg("bias"), py::arg("w_out"), py::arg("want_x") = true, py::arg("logit") = py::none(),
         py::arg("out") = py::none(), "xDeepFM CIN layer in one launch (cin.hip) -> [xk, logit]");
+  m.def("autoint", &autoint, py::arg("x"), py::arg("wpack"), py::arg("opack") = py::none(), py::arg("heads") = 2,
+        py::arg("L") = 1, py::arg("want_x") = true, py::arg("logit") = py::none(), py::arg("out") = py::none(),
+        "AutoInt interacting-layer stack in one launch (autoint.hip) -> [y, logit]");
   m.def("mlp_tail_fp8", &mlp_tail_fp8, py::arg("X"), py::arg("W2p"), py::arg("sw2"), py::arg("b2"), py::arg("act2"),
         py::arg("W3p"), py::arg("sw3"), py::arg("b3"), py::arg("act3"), py::arg("hw"), py::arg("hbias") = 0.0,
         py::arg("extra") = py::none(), py::arg("sigmoid") = true, py::arg("out") = py::none(),

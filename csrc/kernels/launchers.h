@@ -209,6 +209,18 @@ hipError_t launch_cin_layer(const void* x0, int64_t ld0, const void* xp, int64_t
                             const void* Wp, const float* bias, const float* w_out, void* xk, int64_t ldk,
                             float* logit, bool accumulate, hipStream_t st);
 
+// A stack of L AutoInt interacting layers (multi-head self-attention over the F
+// fields, relu residual) in one launch (autoint.hip): x [B, F, 64] bf16 with
+// candidate / row strides ldxb / ldxr in elements (multiples of 8, 16-byte
+// aligned base) -> y = y^L (same form, may be null) and logit[b] (+)= sum_{f,u}
+// w_out[f,u] float(y^L[b,f,u]) (null together with opack). wpack / opack:
+// ops.autoint_pack (L x 4 matrices in fragment order; w_out in fragment order,
+// ceil(F / 16) x 4 KB). accumulate: logit += instead of =. 1 <= F <= 64, heads
+// in {1, 2, 4}, 1 <= L <= 4.
+hipError_t launch_autoint(const void* x, int64_t ldxb, int64_t ldxr, int B, int F, int heads, int L, const void* wpack,
+                          const float* opack, void* y, int64_t ldyb, int64_t ldyr, float* logit, bool accumulate,
+                          hipStream_t st);
+
 // The same tail on the block-scaled fp8 matrix cores (mlp_tail_fp8.hip): x
 // (bf16) and the fp32 h2 are MX-quantised inside the kernel (e4m3 + one E8M0
 // byte per 32 columns), W2p / W3p are e4m3 weights in the fragment order of

@@ -37,7 +37,7 @@ PRESET_DIR = os.path.join(REPO, "configs")
 class ModelConfig:
     """Architecture of one CTR model (random-init weights; see models/)."""
 
-    family: str = "deepfm"            # wdl | deepfm | dcn | dcn_v2 | dlrm | din | xdeepfm
+    family: str = "deepfm"            # wdl | deepfm | dcn | dcn_v2 | dlrm | din | xdeepfm | autoint
     num_fields: int = 43              # reference FIELD_NUM
     vocab_size: int = 1_000_000       # rows of the shared table (wdl/deepfm/dcn/dcn_v2)
     embed_dim: int = 64
@@ -72,6 +72,10 @@ class ModelConfig:
     att_dims: Tuple[int, int] = (80, 40)
     # xdeepfm: feature maps per CIN layer (ops.cin_layer; each <= 256, num_fields <= 64, embed_dim 64 on the GPU)
     cin_dims: Tuple[int, ...] = (128, 128)
+    # autoint: interacting layers (<= 4) and attention heads (1, 2 or 4) of the field self-attention stack
+    # (ops.autoint; num_fields <= 64, embed_dim 64 on the GPU)
+    autoint_layers: int = 3
+    autoint_heads: int = 2
     param_dtype: str = "bf16"         # storage dtype of embeddings + dense weights
     gemm_dtype: str = "bf16"          # bf16 | fp8 (dcn_v2 towers on CDNA4 fp8 MFMA)
     # bf16 | fp8: the last two MLP layers + head as the MX-fp8 fused tail (ops.mlp_tail_fp8);

@@ -1,2 +1,2 @@
 """CTR model families (random-init; see ctr.py)."""
-from .ctr import DCN, DLRM, FAMILIES, CTRModel, DCNv2, DeepFM, WideDeep, XDeepFM, build_model  # noqa: F401
+from .ctr import DCN, DLRM, FAMILIES, AutoInt, CTRModel, DCNv2, DeepFM, WideDeep, XDeepFM, build_model  # noqa: F401

@@ -23,6 +23,7 @@ dcn_v2       sigmoid(w_c . cross_v2^L(emb) + head(MLP(emb)))  (fp8 towers opt.)
 dlrm         sigmoid(head(topMLP(dot(botMLP(dense), emb_t))))
 din          sigmoid(head(MLP([profile | target | attention(target, history)])))
 xdeepfm      sigmoid(lin(ids, wts) + w_o . CIN^L(emb) + head(MLP(emb)))
+autoint      sigmoid(lin(ids, wts) + w_o . attn^L(emb) + head(MLP(emb)))
 ===========  ==========================================================
 """
 from __future__ import annotations
@@ -35,7 +36,7 @@ from torch import nn
 
 from .. import ops
 from ..config import ModelConfig
-from .layers import CIN, DTYPES, MLP, CrossMix, Dense, DinAttention, hashed_uniform_rows_, init_uniform_, make_generator, pad8
+from .layers import CIN, DTYPES, MLP, AutoIntStack, CrossMix, Dense, DinAttention, hashed_uniform_rows_, init_uniform_, make_generator, pad8
 
 
 class CTRModel(nn.Module):
@@ -784,7 +785,40 @@ class XDeepFM(CTRModel):
         return self.mlp.forward_head(x, self.head_w, self.head_b, extra=lin + self.cin(x0), out=out)
 
 
-FAMILIES = {c.family: c for c in (WideDeep, DeepFM, DCN, DCNv2, DLRM, DIN, XDeepFM)}
+class AutoInt(CTRModel):
+    """AutoInt+ (Song et al. 2019) with the first-order term: a stack of
+    multi-head self-attention layers over the [B, F, D] view of the embeddings
+    (ops.autoint, the whole stack in one launch; the output weights w_o [F, D]
+    on the last layer's fields give its logit) and the plain MLP, summed in
+    front of the sigmoid."""
+
+    family = "autoint"
+
+    def __init__(self, cfg: ModelConfig, device="cpu"):
+        super().__init__(cfg, device)
+        V, D, F = cfg.vocab_size, cfg.embed_dim, cfg.num_fields
+        self.emb = self._embedding_table(V, D)
+        self.lin = nn.Parameter(init_uniform_(torch.empty(V, device=self.device_), 0.05, self.gen), requires_grad=False)
+        self.lin_bias = 0.0
+        self.attn = AutoIntStack(F, D, cfg.autoint_heads, cfg.autoint_layers, 1.0 / math.sqrt(3 * D), self.dtype,
+                                 self.device_, self.gen)
+        self.mlp = MLP(F * D, cfg.mlp_dims, self.dtype, self.device_, self.gen)
+        self.head_w = nn.Parameter(init_uniform_(torch.empty(self.mlp.out_dim, device=self.device_), 0.05, self.gen),
+                                   requires_grad=False)
+        self.head_b = 0.0
+
+    def _forward(self, ids, wts, out=None, resolved=None):
+        F, D = self.cfg.num_fields, self.cfg.embed_dim
+        if ids.is_cuda:
+            ops.autoint_check(D, F, self.cfg.autoint_heads, self.cfg.autoint_layers)
+        x, lin = ops.embed(self.emb, ids, wts, lin=self.lin, modulo=self.cfg.vocab_size, bias=self.lin_bias,
+                           want_x=True, want_fm=True, fm2=False)
+        # x [B, F D] (row-strided) viewed in place as [B, F, D]
+        x0 = x.as_strided((x.shape[0], F, D), (x.stride(0), D, 1))
+        return self.mlp.forward_head(x, self.head_w, self.head_b, extra=lin + self.attn(x0), out=out)
+
+
+FAMILIES = {c.family: c for c in (WideDeep, DeepFM, DCN, DCNv2, DLRM, DIN, XDeepFM, AutoInt)}
 
 
 def build_model(cfg: ModelConfig, device="cpu", **kw) -> CTRModel:

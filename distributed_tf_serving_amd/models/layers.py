@@ -303,6 +303,59 @@ class CIN(nn.Module):
         return logit
 
 
+class AutoIntStack(nn.Module):
+    """AutoInt's interacting layers: L layers of (Wq, Wk, Wv, Wres) [D, D]
+    (in -> out) and the output weights w_out fp32 [F, D] on the last layer's
+    fields (ops.autoint). ``x_rms``: the rms of the embeddings' elements. Wv
+    and Wres are drawn so that a layer keeps about that rms, Wq and Wk so that
+    the scores (no 1 / sqrt(d) in the op: the scale is folded in here) have
+    about unit spread on the first layer, and w_out so that the logit has
+    unit-order spread."""
+
+    def __init__(self, F: int, D: int, heads: int, L: int, x_rms: float, dtype, device, gen):
+        super().__init__()
+        if heads < 1 or D % heads:
+            raise ValueError(f"autoint_heads must divide embed_dim = {D}, got {heads}")
+        if L < 1:
+            raise ValueError(f"autoint_layers must be >= 1, got {L}")
+        self.F, self.D, self.heads, self.L = F, D, heads, L
+        d = D // heads
+
+        def mat(std):
+            return nn.Parameter(init_uniform_(torch.empty(D, D, device=device), math.sqrt(3.0) * std, gen).to(dtype),
+                                requires_grad=False)
+
+        sqk = 1.0 / (x_rms * math.sqrt(D) * d ** 0.25)  # q, k elements ~ d^-1/4: a score sums d products
+        self.W = nn.ParameterList([mat(s) for _ in range(L) for s in (sqk, sqk, 1.0 / math.sqrt(D), 1.0 / math.sqrt(D))])
+        self.w_out = nn.Parameter(init_uniform_(torch.empty(F, D, device=device), math.sqrt(3.0) / (x_rms * math.sqrt(F * D)), gen),
+                                  requires_grad=False)
+
+    def raw(self) -> list:
+        return [tuple(self.W[4 * l:4 * l + 4]) for l in range(self.L)]
+
+    def packed(self) -> tuple:
+        """ops.autoint_pack of the stack, re-packed INTO the same buffers
+        whenever a weight changed (see CrossMix.packed)."""
+        ts = list(self.W) + [self.w_out]
+        key = tuple((t.data_ptr(), t._version) for t in ts)
+        cached = self.__dict__.get("_packed")
+        if cached is None or cached[0] != key:
+            fresh = ops.autoint_pack([tuple(t.detach() for t in lw) for lw in self.raw()], self.w_out.detach())
+            if cached is not None and all(o.shape == n.shape and o.device == n.device
+                                          for o, n in zip(cached[1][:2], fresh[:2])):
+                for o, n in zip(cached[1][:2], fresh[:2]):
+                    o.copy_(n)
+                fresh = cached[1]
+            cached = (key, fresh)
+            self.__dict__["_packed"] = cached
+        return cached[1]
+
+    def forward(self, x0: torch.Tensor) -> torch.Tensor:
+        """x0 [B, F, D] (a view) -> the stack's logit fp32 [B]; y^L is not written."""
+        ws = self.packed() if x0.is_cuda else self.raw()
+        return ops.autoint(x0, ws, self.heads, self.w_out, want_x=False)[1]
+
+
 class MLP(nn.Module):
     def __init__(self, in_dim: int, dims: Sequence[int], dtype, device, gen, fp8: bool = False,
                  last_act: str = "relu", in_pad: Optional[int] = None, tail_fp8: bool = False):

@@ -18,7 +18,9 @@ Op inventory: K0 ``pack_ids``, K1 ``embed``, K1b
 (multi-hot bags pooled inside the interaction); through the peer lookup ``dot_interaction_gather_peer`` /
 ``peer_bag`` (bf16 or fp8 stores, by the peer tables' dtype); ``din_attention``
 (DIN: gather + target attention over the history in one launch); ``cin_layer``
-(xDeepFM: one CIN layer per launch, the outer product formed in registers).
+(xDeepFM: one CIN layer per launch, the outer product formed in registers);
+``autoint`` (AutoInt: a stack of multi-head field self-attention layers in one
+launch, operands in registers from x to the output).
 """
 from __future__ import annotations
 
@@ -1344,6 +1346,115 @@ def cin_layer(x0: torch.Tensor, xp: torch.Tensor, weights, bias: torch.Tensor, w
         logit += lg
         lg = logit
     return (xk if want_x else None), lg
+
+
+# ------------------------------------------------------------------ AutoInt
+AUTOINT_MAX_F, AUTOINT_MAX_L, AUTOINT_HEADS = 64, 4, (1, 2, 4)  # csrc/kernels/autoint.hip
+
+
+def autoint_check(D: int, F: int, heads: int, L: int) -> None:
+    """The range csrc/kernels/autoint.hip covers; ValueError names the limit."""
+    if D != 64:
+        raise ValueError(f"autoint needs D = 64 on the GPU, got D = {D}")
+    if not 1 <= F <= AUTOINT_MAX_F:
+        raise ValueError(f"autoint covers 1 <= F <= {AUTOINT_MAX_F}, got F = {F}")
+    if heads not in AUTOINT_HEADS:
+        raise ValueError(f"autoint covers heads in {{1, 2, 4}}, got heads = {heads}")
+    if not 1 <= L <= AUTOINT_MAX_L:
+        raise ValueError(f"autoint covers 1 <= L <= {AUTOINT_MAX_L}, got L = {L}")
+
+
+def autoint_pack(layers, w_out: Optional[torch.Tensor] = None) -> tuple:
+    """The stack's weights as csrc/kernels/autoint.hip keeps them in LDS ->
+    (wpack, opack or None, L). ``layers``: L tuples (Wq, Wk, Wv, Wres) of
+    [64 in, 64 out] bf16. wpack is [L, 4 matrices, 4 unit blocks, 2 K chunks,
+    64 lanes, 8] (:func:`pack_bfrag` of W^T): lane (fr, fq) of fragment
+    (ub, kc) holds W[32 kc + 8 fq .. + 7, unit(ub, fr)], where the output units
+    are permuted inside every group of 32 (block t, fragment row 4 j + s = unit
+    8 j + 4 t + s, as :func:`din_attention_pack` does): a lane's outputs of a
+    block pair are then 8 consecutive units, the next MFMA's fragment. opack:
+    ``w_out`` fp32 [F, 64], rows zero padded to a multiple of 16, as [row
+    block, 32-unit chunk, 64 lanes, 8]: lane (fr, fq) holds w_out[16 mb + fr,
+    32 g + 8 fq .. + 7]."""
+    layers = [tuple(m) for m in layers]
+    autoint_check(64, 1, 1, len(layers))
+    mats = []
+    for lw in layers:
+        if len(lw) != 4 or any(tuple(w.shape) != (64, 64) for w in lw):
+            raise ValueError(f"autoint_pack takes (Wq, Wk, Wv, Wres) of [64, 64] per layer (D = 64), got "
+                             f"{[tuple(w.shape) for w in lw]}")
+        for w in lw:
+            wt = w.detach().to(torch.bfloat16).t()  # [unit, in]
+            mats.append(pack_bfrag(wt.reshape(2, 4, 2, 4, 64).transpose(1, 2).reshape(64, 64)))
+    wpack = torch.stack(mats).reshape(len(layers), 4, 4, 2, 64, 8).contiguous()
+    opack = None
+    if w_out is not None:
+        F = int(w_out.shape[0])
+        if w_out.dim() != 2 or w_out.shape[1] != 64 or not 1 <= F <= AUTOINT_MAX_F:
+            raise ValueError(f"autoint_pack takes w_out [F <= {AUTOINT_MAX_F}, 64], got {tuple(w_out.shape)}")
+        nmb = -(-F // 16)
+        wz = torch.zeros(nmb * 16, 64, dtype=torch.float32, device=w_out.device)
+        wz[:F] = w_out.detach().float()
+        opack = wz.reshape(nmb, 16, 2, 4, 8).permute(0, 2, 3, 1, 4).contiguous()
+    return wpack, opack, len(layers)
+
+
+def autoint(x: torch.Tensor, layers, heads: int, w_out: Optional[torch.Tensor] = None, want_x: bool = True,
+            logit: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
+    """A stack of AutoInt interacting layers (Song et al. 2019): multi-head
+    self-attention over the F fields of every candidate with a relu residual,
+    all L layers in one launch on the GPU (csrc/kernels/autoint.hip; nothing of
+    size F x D or F x F leaves the registers between x and the outputs). Per
+    layer, d = D / heads, head h owning units h d .. h d + d - 1:
+
+        q, k, v   = bf16(x Wq), bf16(x Wk), bf16(x Wv)        fp32 sums, one rounding each
+        s_h[i, j] = q_h[i] . k_h[j]                           fp32, no 1 / sqrt(d): fold a scale into Wq
+        e_h[i, j] = exp(s_h[i, j] - max_j s_h[i, j])
+        o_h[i]    = (sum_j bf16(e_h[i, j]) v_h[j]) / sum_j e_h[i, j]
+        y[i]      = bf16(relu(concat_h o_h[i] + x[i] Wres))   the residual product stays fp32
+
+    and ``logit[b] (+)= sum_{f, u} w_out[f, u] float(y^L[b, f, u])``. ``x``
+    bf16 [B, F, D], possibly a strided view with 16-byte aligned rows.
+    ``layers``: L tuples (Wq, Wk, Wv, Wres) of [D, D] bf16 (in -> out) or, on
+    the GPU, :func:`autoint_pack` of them (then ``w_out`` is the one packed
+    there). ``w_out`` fp32 [F, D] or None (no logit). Returns (y^L or None,
+    logit or None); ``out`` receives y^L, a given ``logit`` is accumulated
+    into. GPU: D = 64, F <= 64, heads in {1, 2, 4}, L <= 4
+    (:func:`autoint_check`). CPU: the same contract in fp32 torch ops, any D
+    divisible by ``heads``."""
+    B, F, D = (int(s) for s in x.shape)
+    packed = len(layers) == 3 and isinstance(layers[2], int)
+    if x.is_cuda:
+        L = layers[2] if packed else len(layers)
+        autoint_check(D, F, heads, L)
+        if x.stride(2) != 1 or (F > 1 and x.stride(1) % 8) or (B > 1 and x.stride(0) % 8) or x.data_ptr() % 16:
+            raise ValueError(f"autoint needs 16-byte aligned rows: x strides {tuple(x.stride())} (elements)")
+        wpack, opack, _ = layers if packed else autoint_pack(layers, w_out)
+        y, lg = hip().autoint(x, wpack, opack, int(heads), L, want_x, logit, out)
+        return (y if want_x else None), (lg if opack is not None else None)
+    if packed:
+        raise ValueError("autoint on the CPU takes the raw (Wq, Wk, Wv, Wres) per layer")
+    if heads < 1 or D % heads:
+        raise ValueError(f"autoint: D = {D} is not divisible by heads = {heads}")
+    rb = lambda t: t.to(torch.bfloat16).float()  # noqa: E731
+    y = x
+    for Wq, Wk, Wv, Wr in layers:
+        xf = y.float()
+        q, k, v = (rb(xf @ W.float()).view(B, F, heads, D // heads).transpose(1, 2) for W in (Wq, Wk, Wv))
+        s = q @ k.transpose(-1, -2)
+        e = torch.exp(s - s.amax(dim=-1, keepdim=True))
+        o = (rb(e) @ v) / e.sum(dim=-1, keepdim=True)
+        y = torch.relu(o.transpose(1, 2).reshape(B, F, D) + xf @ Wr.float()).to(torch.bfloat16)
+    lg = None
+    if w_out is not None:
+        lg = (y.float() * w_out.float()).sum(dim=(1, 2))
+        if logit is not None:
+            logit += lg
+            lg = logit
+    if want_x and out is not None:
+        out.copy_(y)
+        y = out
+    return (y.to(x.dtype) if want_x else None), lg
 
 
 def unpack_bfrag(Wp: torch.Tensor, N: int, K: int) -> torch.Tensor:
